@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: hybrid retrieval queries/sec on a 1M x 768 corpus (BASELINE.json configs[2]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,14 +18,18 @@ queries are enqueued back to back with no host synchronisation in between.
 N > 1: the SAME corpus row-sharded N ways -- the synthetic corpus is a function of (seed, global row)
 (a-nice-rag_amd/synth.py), so the union of the shards is bit-identical to the N = 1 corpus and the queries
 are the same: per-rank legs, one RCCL all-gather of 2 x 25 candidate records per rank and query on a
-communication stream, replicated merge + fusion (a-nice-rag_amd/sharded.py).  After the timed region rank 0
-builds a SINGLE index over the whole corpus and checks the sharded answers of 8 queries against it
+communication stream, replicated merge + fusion (a-nice-rag_amd/sharded.py).  With `--full`, after the timed region
+rank 0 builds a SINGLE index over the whole corpus and checks the sharded answers of 8 queries against it
 (`sharded_matches_single`).  Default: strong scaling of the 1M-row corpus (the metric's "1M x 768 corpus, 1/2/4/8
 MI355X"); `--rows-per-gpu R` = weak scaling (C5: `--rows-per-gpu 1000000 --dim 1024` on 8 GPUs = 8M x 1024).
 
-Prints ONE JSON line on rank 0 (fields of the build contract + `roofline` + `cpu_baseline` + `also`: the C2 / C4 /
-K3 / tail measurements of the same run, each with what it takes to recompute its roofline fraction).
-Exit code 1 when a parity check fails (GPU vs CPU port, sharded vs single index).
+Prints ONE JSON line on rank 0: the fields of the build contract (`metric`, `value`, `unit`, `ms_per_step`, ...).
+A plain run does only what they need: set up, warm up, time `--steps` steps.  `--dump-outputs DIR` then writes what
+the timed path returned in its last step as DIR/<name>.npy (float64; the inputs are seeded, so two builds can be
+compared output for output).  `--full` adds everything else to the same line: `roofline` (HIP events on sampled K1
+launches inside the timed region), `latency_us`, `cpu_baseline` + `recall_at_10` (CPU port and parity check),
+`also` (the C2 / C4 / K3 / tail measurements, each with what it takes to recompute its roofline fraction) and, N > 1,
+`sharded_matches_single`.  Exit code 1 when one of those parity checks fails (GPU vs CPU port, sharded vs single index).
 """
 from __future__ import annotations
 
@@ -73,11 +77,18 @@ def parse_args(argv=None):
     ap.add_argument("--filter", action="store_true",
                     help="diagnostic: source-prefix filter as retrieval_eval.py:280 passes it ('CG,NG'); rows "
                          "carry one of 300 source ids, 15 %% of them outside the filter (SURVEY.md 8d)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-queries", type=int, default=12, help="queries of the bounded CPU sample")
-    ap.add_argument("--no-also", action="store_true", help="skip the C2 / C4 / K3 side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as "
+                         "DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: roofline, latency, CPU port and "
+                         "parity, recall@10, the C2 / C4 / K3 side measurements, the sharded-vs-single check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU port")
+    ap.add_argument("--cpu-queries", type=int, default=12, help="queries of the bounded CPU sample (--full)")
+    ap.add_argument("--no-also", action="store_true", help="--full without the C2 / C4 / K3 side measurements")
     ap.add_argument("--check-queries", type=int, default=8,
-                    help="N > 1: queries of the sharded answer checked against a single index on rank 0 (0 = off)")
+                    help="--full, N > 1: queries of the sharded answer checked against a single index on rank 0 "
+                         "(0 = off)")
     ap.add_argument("--launch-selftest", action="store_true",
                     help="test hook (tests/test_bench_launcher.py): the ranks run on the CPU over gloo and only "
                          "check the launcher, the rendezvous and the block-seeded corpus generator")
@@ -332,46 +343,53 @@ def run_rank(args) -> int:
     if sharded and args.warmup == 0:
         step(0)  # the first all-gather sets the collective up: never inside the timed region
     finish()
-    # HIP events around the dominant kernel only, on a SAMPLE of its launches, on the stream it is launched on: a
-    # bracket holds its stream for ~10 us, which at batch=1 would be charged to every query (measured: 463 -> 452
-    # us/step at 1M rows; a sharded K1 launch carries a whole exchange group and paid 10 us per 2 launches = 2 % at the
-    # 125k-row shard): every 8th launch here, every launch in the separate pass below.
     main_kernel = nat.KERNEL_DENSE_BATCHED if batched else nat.KERNEL_DENSE_SCAN
-    idx.profile(True, kernels=[main_kernel], every=1 if batched else 8)
-    idx.profile_reset()
+    if args.full:
+        # HIP events around the dominant kernel only, on a SAMPLE of its launches, on the stream it is launched on: a
+        # bracket holds its stream for ~10 us, which at batch=1 would be charged to every query (measured: 463 -> 452
+        # us/step at 1M rows; a sharded K1 launch carries a whole exchange group and paid 10 us per 2 launches = 2 % at
+        # the 125k-row shard): every 8th launch here, every launch in the separate pass below.
+        idx.profile(True, kernels=[main_kernel], every=1 if batched else 8)
+        idx.profile_reset()
     barrier()
     t0 = time.perf_counter()
+    ticket = None
     for i in range(args.steps):
-        step(i)
+        ticket = step(i)
     finish()
     barrier()
     elapsed = time.perf_counter() - t0
-    scan_ms, scan_n = idx.profile_read(main_kernel)
-    scan_units = idx.profile_units(main_kernel)  # queries the timed launches carried (sharded: a group per K1 launch)
-    sampled = "every %s launch of the timed region" % ("" if batched else "8th")
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # a short timed region leaves a handful of bracketed launches: add a separate pass, outside the timed region,
-    # in which EVERY launch of the kernel is bracketed, so that the roofline never rests on three samples
-    MIN_SAMPLES = 32
-    if scan_n < MIN_SAMPLES and not batched:
-        extra = 64 * (args.exchange_group if sharded else 1)
-        idx.profile(True, kernels=[main_kernel], every=1)
-        for i in range(extra):
-            step(i)
-        finish()
-        barrier()
+    # before anything else runs a step: the passes below write the same output buffers
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step_outputs(args, searcher, ticket, out, cnt, hybrid, batched))
+
+    if args.full:
         scan_ms, scan_n = idx.profile_read(main_kernel)
-        scan_units = idx.profile_units(main_kernel)
-        sampled += " + every launch of a %d-query pass after it" % extra
-    idx.profile(False)
+        scan_units = idx.profile_units(main_kernel)  # queries the timed launches carried (sharded: a group per launch)
+        sampled = "every %s launch of the timed region" % ("" if batched else "8th")
+        # a short timed region leaves a handful of bracketed launches: add a separate pass, outside the timed region,
+        # in which EVERY launch of the kernel is bracketed, so that the roofline never rests on three samples
+        MIN_SAMPLES = 32
+        if scan_n < MIN_SAMPLES and not batched:
+            extra = 64 * (args.exchange_group if sharded else 1)
+            idx.profile(True, kernels=[main_kernel], every=1)
+            for i in range(extra):
+                step(i)
+            finish()
+            barrier()
+            scan_ms, scan_n = idx.profile_read(main_kernel)
+            scan_units = idx.profile_units(main_kernel)
+            sampled += " + every launch of a %d-query pass after it" % extra
+        idx.profile(False)
 
     # single-query latency (SURVEY.md 8d asks for p50/p99 next to the throughput): one query in flight,
     # enqueue -> all streams idle, host clock.  Outside the timed region.
     latency = None
-    if not sharded and not batched:
+    if args.full and not sharded and not batched:
         lat = []
         for i in range(200):
             torch.cuda.synchronize()
@@ -386,7 +404,7 @@ def run_rank(args) -> int:
     # ------------------------------------------------------------------ sharded answer == single-index answer
     ok = True
     shard_check = None
-    if sharded and args.check_queries > 0:
+    if args.full and sharded and args.check_queries > 0:
         nq = min(args.check_queries, args.queries)
         tickets = [step(i) for i in range(nq)]
         finish()
@@ -400,13 +418,6 @@ def run_rank(args) -> int:
 
     # ------------------------------------------------------------------ report (rank 0)
     if rank == 0:
-        scan_avg_ms = scan_ms / max(scan_n, 1)
-        # N*D*4 per query (this rank's rows), + N*2 with a filter
-        per_query_bytes = n_local * args.dim * 4 + (n_local * 2 if args.filter else 0)
-        queries_per_launch = (scan_units / scan_n) if (scan_n and not batched) else 1.0
-        alg_bytes = per_query_bytes * queries_per_launch  # a K1 launch of the sharded path scans a GROUP of queries,
-        achieved = alg_bytes / (scan_avg_ms * 1e-3) / 1e9 if scan_n else 0.0  # each its own pass over the shard
-        traffic, traffic_source = carried_traffic(n_local, args.dim, queries_per_launch)
         per_step = args.batch if batched else 1
         line = {
             "metric": "queries/sec, hybrid (dense + BM25) RRF top-10 at batch=1, %s corpus" % (
@@ -422,7 +433,7 @@ def run_rank(args) -> int:
             "higher_is_better": True,
             "scaling": "weak" if weak else "strong",
             "vs_baseline": None,
-            "dtype": "f32",
+            "dtype": "bf16x3" if batched and args.batch_precision == "bf16x3" else "f32",
             "data": "synthetic",
             "config": {
                 "workload": (("C5-shaped" if weak else "C3") + ": %d x %d hybrid (dense + BM25 CSR postings) RRF top-%d, batch=1"
@@ -438,26 +449,35 @@ def run_rank(args) -> int:
                 "bm25_arith": "f64", "source_filter": "CG,NG-shaped: 255 of 300 source ids allowed" if args.filter else None,
                 "corpus": "block-seeded: a function of (seed, global row), identical for every --gpus",
             },
-            "roofline": {
-                "kernel": "dense_scan_kernel (K1)", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": scan_avg_ms, "launches": scan_n,
-                "queries_per_launch": queries_per_launch, "sampled": sampled,
-            },
-            "index_build_s": build_s,
         }
+        if args.full:
+            scan_avg_ms = scan_ms / max(scan_n, 1)
+            if batched:
+                line["roofline"] = batched_roofline(args.batch, n_local, args.dim, scan_avg_ms, scan_n,
+                                                    args.batch_precision == "bf16x3")
+            else:
+                # N*D*4 per query (this rank's rows), + N*2 with a filter
+                per_query_bytes = n_local * args.dim * 4 + (n_local * 2 if args.filter else 0)
+                queries_per_launch = (scan_units / scan_n) if scan_n else 1.0
+                alg_bytes = per_query_bytes * queries_per_launch  # a K1 launch of the sharded path scans a GROUP of
+                achieved = alg_bytes / (scan_avg_ms * 1e-3) / 1e9 if scan_n else 0.0  # queries, each its own pass
+                traffic, traffic_source = carried_traffic(n_local, args.dim, queries_per_launch)
+                line["roofline"] = {
+                    "kernel": "dense_scan_kernel (K1)", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                    "traffic_source": traffic_source, "algorithmic_bytes_per_launch": alg_bytes,
+                    "avg_launch_ms": scan_avg_ms, "launches": scan_n, "queries_per_launch": queries_per_launch,
+                    "sampled": sampled,
+                }
+        line["index_build_s"] = build_s
         if latency:
             line["latency_us"] = latency
         if shard_check:
             line.update(shard_check)
-        if batched:
-            line["roofline"] = batched_roofline(args.batch, n_local, args.dim, scan_avg_ms, scan_n,
-                                                args.batch_precision == "bf16x3")
-            line["dtype"] = "bf16x3" if args.batch_precision == "bf16x3" else "f32"
-        if not sharded and hybrid and not args.no_also and not args.filter:
+        if args.full and not sharded and hybrid and not args.no_also and not args.filter:
             line["also"] = also_measurements(args, torch, nat, lib, idx, Index, synth, E, Q, T, n_terms, post, device,
                                              local_rank, K, TOPN)
-        if not sharded and not args.no_cpu_baseline and not batched:
+        if args.full and not sharded and not args.no_cpu_baseline and not batched:
             line["cpu_baseline"] = cpu_baseline(args, E, Q, post, idf, avgdl, term_lists, out, cnt, hybrid, K, TOPN,
                                                 (W_DENSE, W_BM25, WRRF_K), allowed_rows)
             line["recall_at_10"] = line["cpu_baseline"].pop("niceqa_recall_at_10")
@@ -471,6 +491,31 @@ def run_rank(args) -> int:
               file=sys.stderr, flush=True)
         return 1
     return 0
+
+
+def last_step_outputs(args, searcher, ticket, out, cnt, hybrid, batched):
+    """What a caller of the timed path holds after its last step (the device has finished it): doc ids and fp64
+    scores of the fused (hybrid) or dense top-n, plus the record count (hybrid) or the overflow flags (batched)."""
+    if searcher is not None:
+        ids, scores = searcher.result(ticket)
+        return {"ids": ids, "scores": scores, "count": np.array([len(ids)])}
+    if batched:  # one step = one pass over all args.batch queries
+        rec = out.cpu().numpy()
+        return {"ids": rec[:, :, 1], "scores": rec[:, :, 0].copy().view(np.float64), "flag": cnt.cpu().numpy()}
+    qi = (args.steps - 1) % args.queries
+    n = int(cnt[qi].item()) if hybrid else args.top_n
+    rec = out[qi, :n].cpu().numpy()
+    res = {"ids": rec[:, 1], "scores": rec[:, 0].copy().view(np.float64)}
+    if hybrid:
+        res["count"] = np.array([n])
+    return res
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy as float64 (doc ids < 2^53 are exact): at most --batch x --top-n records, a few KB."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def carried_traffic(n_rows, dim, queries_per_launch):

@@ -8,17 +8,17 @@ O=$R/gpurun_out/r02
 rm -rf $O; mkdir -p $O
 cd $R
 git rev-parse --short HEAD > $O/commit.txt 2>/dev/null || echo unknown > $O/commit.txt
-python bench.py > $O/bench_hybrid_1Mx768.json 2> $O/bench_hybrid.err
+python bench.py --full > $O/bench_hybrid_1Mx768.json 2> $O/bench_hybrid.err
 echo "bench done"
-python bench.py --filter --no-cpu-baseline > $O/bench_hybrid_filter_1Mx768.json 2>/dev/null
-python bench.py --rows 1000000 --dim 1024 --no-cpu-baseline --no-also > $O/bench_c5_one_rank_1Mx1024.json 2>/dev/null
+python bench.py --full --filter --no-cpu-baseline > $O/bench_hybrid_filter_1Mx768.json 2>/dev/null
+python bench.py --full --rows 1000000 --dim 1024 --no-cpu-baseline --no-also > $O/bench_c5_one_rank_1Mx1024.json 2>/dev/null
 for rows in 500000 250000 125000; do
-  ANRAG_FORCE_SHARDED=1 python bench.py --rows $rows --steps 2000 --warmup 200 > $O/bench_shard_rehearsal_${rows}_rows.json 2>/dev/null
+  ANRAG_FORCE_SHARDED=1 python bench.py --full --rows $rows --steps 2000 --warmup 200 > $O/bench_shard_rehearsal_${rows}_rows.json 2>/dev/null
 done
 echo "rehearsals done"
 cd /tmp && export TMPDIR=/tmp
 # 1. kernel trace + stats of the default bench command (no counters in this run)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o hybrid -- python3 $R/bench.py --no-cpu-baseline --no-also \
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o hybrid -- python3 $R/bench.py --full --no-cpu-baseline --no-also \
   > $O/bench_hybrid_under_rocprofv3.json 2> $O/rocprof_bench.err
 find $O/prof_bench -name "*kernel_stats.csv" -exec cp {} $O/bench_hybrid_1Mx768_kernel_stats.csv \;
 echo "trace done"
