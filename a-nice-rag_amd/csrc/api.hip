@@ -224,6 +224,19 @@ int settle_pipeline(anrag_index *idx) {
 constexpr int kScanLanesDefault = 4;
 constexpr int64_t kScanLanesMaxBytes = 1ll << 30;
 
+// The dense prefilter's mode applied to the loaded corpus (anrag_set_dense_prefilter): auto builds it past
+// kScanLanesMaxBytes of fp32 corpus and stays on K1 when it cannot allocate; mode 1 reports ANRAG_ERR_NOMEM.
+static int apply_dense_prefilter(anrag_index *idx) {
+    idx->pf_on = false;
+    if (!idx->d_emb || idx->pf_mode == 0 || !dense_prefilter_has_shape(idx)) return ANRAG_OK;
+    if (idx->pf_mode < 0 && (int64_t)idx->n_rows * idx->dim * 4 <= kScanLanesMaxBytes) return ANRAG_OK;
+    const int rc = build_dense_prefilter(idx);
+    if (rc == ANRAG_ERR_NOMEM && idx->pf_mode < 0) return ANRAG_OK;
+    if (rc) return rc;
+    idx->pf_on = true;
+    return ANRAG_OK;
+}
+
 #define ANRAG_ENTER(idx)                                                   \
     ANRAG_REQUIRE((idx) != nullptr, "index handle is NULL");              \
     std::lock_guard<std::mutex> lock__((idx)->mu);                        \
@@ -289,6 +302,7 @@ int anrag_index_create(int device, anrag_index **out) {
     }
     idx->n_lanes = kScanLanesDefault;
     if (const char *env = getenv("ANRAG_SCAN_LANES")) { const int v = atoi(env); idx->n_lanes = v <= 0 ? 0 : (v >= 4 ? 4 : (v == 3 ? 2 : v)); }
+    if (const char *env = getenv("ANRAG_DENSE_PREFILTER")) { const int v = atoi(env); idx->pf_mode = v < 0 ? -1 : (v > 0 ? 1 : 0); }
     for (int b = 0; b < kPipeSlots && e == hipSuccess; ++b) {
         e = hipEventCreateWithFlags(&idx->ev_scan[b], hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&idx->ev_bm25[b], hipEventDisableTiming);
@@ -310,6 +324,8 @@ static void free_host_slots(anrag_index *idx);
 
 static void free_dense(anrag_index *idx) {
     free_batched(idx);
+    free_dense_prefilter(idx);
+    idx->pf_on = false;
     dev_free(idx, idx->d_dense_scores_f64, idx->n_rows);
     dev_free(idx, idx->d_emb, idx->n_rows * idx->dim);
     dev_free(idx, idx->d_dense_src, idx->n_rows);
@@ -435,7 +451,7 @@ int anrag_dense_load(anrag_index *idx, const float *embeddings, int64_t n_rows, 
         if ((rc = dev_alloc(idx, &idx->d_blk_row_a, (int64_t)kPipeSlots * kMaxScanLists * kListLen))) return rc;
     }
     if ((rc = ensure_query_buffer(idx, (int64_t)64 * dim))) return rc;
-    return ANRAG_OK;
+    return apply_dense_prefilter(idx);
 }
 
 struct GroupQuery {
@@ -622,6 +638,28 @@ int anrag_set_batched_precision(anrag_index *idx, int32_t mode) {
     ANRAG_ENTER(idx);
     ANRAG_REQUIRE(mode == 0 || mode == 1, "mode must be 0 (exact f32 MFMA) or 1 (bf16 x 3 split products)");
     idx->batched_split = mode == 1;
+    return ANRAG_OK;
+}
+
+int anrag_set_dense_prefilter(anrag_index *idx, int32_t mode) {
+    ANRAG_ENTER(idx);
+    ANRAG_REQUIRE(mode >= -1 && mode <= 1, "mode must be -1 (auto), 0 (off) or 1 (on)");
+    ANRAG_REQUIRE(mode != 1 || !idx->d_emb || dense_prefilter_has_shape(idx),
+                  "dense prefilter: no kernel shape for dim %d", idx->dim);
+    int rc = sync_all(idx);  // queries in flight use the current route's buffers
+    if (rc) return rc;
+    idx->pf_mode = mode;
+    return apply_dense_prefilter(idx);
+}
+
+int anrag_dense_prefilter_stats(anrag_index *idx, int64_t *queries, int64_t *survivors) {
+    ANRAG_ENTER(idx);
+    int rc = sync_all(idx);
+    if (rc) return rc;
+    unsigned long long s = 0;
+    if (idx->d_pf_survivors) ANRAG_HIP(hipMemcpy(&s, idx->d_pf_survivors, sizeof(s), hipMemcpyDeviceToHost));
+    if (queries) *queries = idx->pf_queries;
+    if (survivors) *survivors = (int64_t)s;
     return ANRAG_OK;
 }
 

@@ -41,45 +41,6 @@ struct ScanQueries {
     int32_t n;
 };
 
-// The list merge of the PREVIOUS single query of the same stream, done by one extra workgroup of this launch (the
-// lists are complete: the launch that wrote them has finished).  A query submitted alone used to cost a marker on the
-// scans' stream plus a merge kernel on another stream waiting for it: hipEventRecord alone is 4-5 us of stream time per
-// query on this stack (scripts/exp/launch_gap.hip), a tenth of a 100k-row pass.  out == nullptr: nothing to merge.
-struct DeferredTail {
-    const float *blk_s;
-    const uint32_t *blk_r;
-    int32_t n_lists, k;
-    const int64_t *doc;
-    int64_t base;
-    anrag_candidate *out;
-};
-
-// 4 waves: the dense half of query_tail_kernel (tail.hip) -- same merge network, same records
-__device__ __forceinline__ void dense_tail_block(const DeferredTail &dt) {
-    __shared__ float lf_s[4 * kListLen];
-    __shared__ uint32_t lf_r[4 * kListLen];
-    const int lane = lane_id(), wave = threadIdx.x / kWave;
-    WaveTopK<float> tf;
-    tf.init(dt.k);
-    merge_lists(tf, dt.blk_s, dt.blk_r, dt.n_lists, dt.k, wave, 4);
-    for (int half = 2; half >= 1; half >>= 1) {
-        if (wave >= half && wave < 2 * half) {
-            lf_s[wave * kListLen + lane] = tf.s;
-            lf_r[wave * kListLen + lane] = tf.r;
-        }
-        __syncthreads();
-        if (wave < half) tf.merge_sorted(lf_s + (wave + half) * kListLen, lf_r + (wave + half) * kListLen);
-        __syncthreads();
-    }
-    if (wave == 0 && lane < dt.k) {
-        const bool empty = tf.r == kNoRow;
-        anrag_candidate c;
-        c.doc = empty ? -1 : (dt.doc ? dt.doc[tf.r] : dt.base + (int64_t)tf.r);
-        c.score = empty ? -__builtin_huge_val() : (double)tf.s;
-        dt.out[lane] = c;
-    }
-}
-
 template <int G, int CH, int R, bool FILTER, bool SCORES, int THREADS = kScanThreads>
 __global__ __launch_bounds__(THREADS) void dense_scan_kernel(
     const float *__restrict__ emb, ScanQueries Q, int64_t n_rows, int32_t dim, int32_t k,
@@ -411,9 +372,11 @@ int dense_scan_grid(const anrag_index *idx) {
     return grid;
 }
 
-// VGPRs of the scan kernel this index's queries run (the filtered top-k variant: the larger one).  K3 sizes its
-// workgroups so that they fit NEXT TO a scan wave on every SIMD (bm25.hip).
+// VGPRs of the scan kernel this index's queries run (the filtered top-k variant: the larger one; with the prefilter on,
+// the largest of its kernels that run beside K3).  K3 sizes its workgroups so that they fit NEXT TO a scan wave on every
+// SIMD (bm25.hip).
 int dense_scan_vgprs(const anrag_index *idx) {
+    if (idx->pf_on) return dense_prefilter_vgprs(idx);
     int regs = 128;
     const bool known = scan_dispatch(idx->dim, [&](auto shape) {
         using S = decltype(shape);
@@ -472,6 +435,10 @@ int launch_dense_scan_group(anrag_index *idx, hipStream_t st, const float *const
     const int d = idx->dim;
     const int grid = dense_scan_grid(idx);
     const uint32_t *allow = (idx->d_dense_src != nullptr) ? d_allow_bits : nullptr;
+    if (!d_scores_out && k >= 1 && k <= kListLen && idx->pf_on) {  // K1F: fp16 shadow scan + exact rescoring (same lists)
+        LaunchTimer t(idx, ANRAG_KERNEL_DENSE_SCAN, st, n_queries);
+        return launch_dense_prefilter_group(idx, st, d_queries, n_queries, k, allow, sets, dt);
+    }
     {
         LaunchTimer t(idx, ANRAG_KERNEL_DENSE_SCAN, st, n_queries);
         const bool done = scan_dispatch(d, [&](auto shape) {

@@ -2,6 +2,7 @@
 // both, which is what makes a tile score equal the scan's score bit for bit -- and the dimension -> kernel shape table.
 #pragma once
 #include "common.hpp"
+#include "wave_topk.hpp"
 
 namespace anrag {
 
@@ -90,6 +91,45 @@ inline bool scan_dispatch(int d, F &&f) {
         }
     }
     return false;
+}
+
+// The list merge of the PREVIOUS single query of the same stream, done by one extra workgroup of this launch (the
+// lists are complete: the launch that wrote them has finished).  A query submitted alone used to cost a marker on the
+// scans' stream plus a merge kernel on another stream waiting for it: hipEventRecord alone is 4-5 us of stream time per
+// query on this stack (scripts/exp/launch_gap.hip), a tenth of a 100k-row pass.  out == nullptr: nothing to merge.
+struct DeferredTail {
+    const float *blk_s;
+    const uint32_t *blk_r;
+    int32_t n_lists, k;
+    const int64_t *doc;
+    int64_t base;
+    anrag_candidate *out;
+};
+
+// 4 waves: the dense half of query_tail_kernel (tail.hip) -- same merge network, same records
+__device__ __forceinline__ void dense_tail_block(const DeferredTail &dt) {
+    __shared__ float lf_s[4 * kListLen];
+    __shared__ uint32_t lf_r[4 * kListLen];
+    const int lane = lane_id(), wave = threadIdx.x / kWave;
+    WaveTopK<float> tf;
+    tf.init(dt.k);
+    merge_lists(tf, dt.blk_s, dt.blk_r, dt.n_lists, dt.k, wave, 4);
+    for (int half = 2; half >= 1; half >>= 1) {
+        if (wave >= half && wave < 2 * half) {
+            lf_s[wave * kListLen + lane] = tf.s;
+            lf_r[wave * kListLen + lane] = tf.r;
+        }
+        __syncthreads();
+        if (wave < half) tf.merge_sorted(lf_s + (wave + half) * kListLen, lf_r + (wave + half) * kListLen);
+        __syncthreads();
+    }
+    if (wave == 0 && lane < dt.k) {
+        const bool empty = tf.r == kNoRow;
+        anrag_candidate c;
+        c.doc = empty ? -1 : (dt.doc ? dt.doc[tf.r] : dt.base + (int64_t)tf.r);
+        c.score = empty ? -__builtin_huge_val() : (double)tf.s;
+        dt.out[lane] = c;
+    }
 }
 
 }  // namespace anrag
