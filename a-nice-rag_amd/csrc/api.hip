@@ -224,13 +224,14 @@ int settle_pipeline(anrag_index *idx) {
 constexpr int kScanLanesDefault = 4;
 constexpr int64_t kScanLanesMaxBytes = 1ll << 30;
 
-// The dense prefilter's mode applied to the loaded corpus (anrag_set_dense_prefilter): auto builds it past
-// kScanLanesMaxBytes of fp32 corpus and stays on K1 when it cannot allocate; mode 1 reports ANRAG_ERR_NOMEM.
+// The dense prefilter's mode applied to the loaded corpus (anrag_set_dense_prefilter): auto builds the int8 form past
+// kScanLanesMaxBytes of fp32 corpus and stays on K1 when it cannot allocate; modes 1 (fp16) and 2 (int8) report
+// ANRAG_ERR_NOMEM.
 static int apply_dense_prefilter(anrag_index *idx) {
     idx->pf_on = false;
     if (!idx->d_emb || idx->pf_mode == 0 || !dense_prefilter_has_shape(idx)) return ANRAG_OK;
     if (idx->pf_mode < 0 && (int64_t)idx->n_rows * idx->dim * 4 <= kScanLanesMaxBytes) return ANRAG_OK;
-    const int rc = build_dense_prefilter(idx);
+    const int rc = build_dense_prefilter(idx, idx->pf_mode == 1 ? kPrefilterFp16 : kPrefilterInt8);
     if (rc == ANRAG_ERR_NOMEM && idx->pf_mode < 0) return ANRAG_OK;
     if (rc) return rc;
     idx->pf_on = true;
@@ -302,7 +303,7 @@ int anrag_index_create(int device, anrag_index **out) {
     }
     idx->n_lanes = kScanLanesDefault;
     if (const char *env = getenv("ANRAG_SCAN_LANES")) { const int v = atoi(env); idx->n_lanes = v <= 0 ? 0 : (v >= 4 ? 4 : (v == 3 ? 2 : v)); }
-    if (const char *env = getenv("ANRAG_DENSE_PREFILTER")) { const int v = atoi(env); idx->pf_mode = v < 0 ? -1 : (v > 0 ? 1 : 0); }
+    if (const char *env = getenv("ANRAG_DENSE_PREFILTER")) { const int v = atoi(env); idx->pf_mode = v < 0 ? -1 : (v > 2 ? 2 : v); }
     for (int b = 0; b < kPipeSlots && e == hipSuccess; ++b) {
         e = hipEventCreateWithFlags(&idx->ev_scan[b], hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&idx->ev_bm25[b], hipEventDisableTiming);
@@ -643,8 +644,8 @@ int anrag_set_batched_precision(anrag_index *idx, int32_t mode) {
 
 int anrag_set_dense_prefilter(anrag_index *idx, int32_t mode) {
     ANRAG_ENTER(idx);
-    ANRAG_REQUIRE(mode >= -1 && mode <= 1, "mode must be -1 (auto), 0 (off) or 1 (on)");
-    ANRAG_REQUIRE(mode != 1 || !idx->d_emb || dense_prefilter_has_shape(idx),
+    ANRAG_REQUIRE(mode >= -1 && mode <= 2, "mode must be -1 (auto), 0 (off), 1 (fp16) or 2 (int8)");
+    ANRAG_REQUIRE(mode <= 0 || !idx->d_emb || dense_prefilter_has_shape(idx),
                   "dense prefilter: no kernel shape for dim %d", idx->dim);
     int rc = sync_all(idx);  // queries in flight use the current route's buffers
     if (rc) return rc;

@@ -228,14 +228,16 @@ struct anrag_index {
     void *call_pin = nullptr;           // pinned staging of the same calls
     int64_t call_pin_bytes = 0;
 
-    // dense prefilter (dense_prefilter.hip): an fp16 shadow of the corpus, per-row error radii, and per list set the
-    // rows' score upper bounds and the threshold T -- one block, dropped by the next dense load / the destroy
-    int32_t pf_mode = -1;               // -1 auto (on past kScanLanesMaxBytes of fp32 corpus), 0 off, 1 on
+    // dense prefilter (dense_prefilter.hip): an fp16 or int8 shadow of the corpus, its per-row data, and per list set
+    // the rows' score upper bounds and the threshold T -- one block of one form, dropped by the next dense load / the
+    // destroy, or replaced when the mode asks for the other form
+    int32_t pf_mode = -1;               // -1 auto (int8, past kScanLanesMaxBytes of fp32 corpus), 0 off, 1 fp16, 2 int8
     bool pf_on = false;
+    int32_t pf_form = 0;                // form of pf_block: 0 none, kPrefilterFp16, kPrefilterInt8
     void *pf_block = nullptr;
     int64_t pf_bytes = 0;
-    void *d_pf_img = nullptr;           // n_rows x dim fp16
-    float *d_pf_m = nullptr;            // n_rows radii
+    void *d_pf_img = nullptr;           // n_rows x dim fp16 / int8
+    float *d_pf_m = nullptr;            // fp16: n_rows radii; int8: n_rows x {s_e, m1, m2, 0}
     float *d_pf_hi = nullptr;           // [kPipeSlots][pf_hi_stride]
     int64_t pf_hi_stride = 0;
     float *d_pf_thr = nullptr;          // [kPipeSlots]
@@ -300,11 +302,14 @@ int dense_tile_mfma_block_rows(const anrag_index *idx);   // rows per block of t
 int launch_dense_tile_mfma(anrag_index *idx, hipStream_t stream, const float *d_queries, int64_t q_stride, int32_t n_queries,
                            const uint32_t *d_allow_bits, float *d_scores_out, int64_t scores_stride);
 bool dense_scan_has_shape(const anrag_index *idx);  // a shaped (not the generic) scan kernel serves this dimension
-// K1F, the prefiltered dense top-k (dense_prefilter.hip): fp16 shadow scan -> threshold -> exact rescoring of survivors
+// K1F / K1F8, the prefiltered dense top-k (dense_prefilter.hip): fp16 or int8 shadow scan -> threshold -> exact
+// rescoring of survivors
 bool dense_prefilter_has_shape(const anrag_index *idx);
 int dense_prefilter_vgprs(const anrag_index *idx);  // the largest K1F kernel that runs beside K3 (0: no shape)
-int64_t dense_prefilter_bytes(int64_t n_rows, int32_t dim);
-int build_dense_prefilter(anrag_index *idx);  // allocate + convert (syncs the primary stream); no-op when built
+constexpr int32_t kPrefilterFp16 = 1, kPrefilterInt8 = 2;  // the forms (K1F, K1F8): anrag_set_dense_prefilter's modes
+int64_t dense_prefilter_bytes(int64_t n_rows, int32_t dim, int32_t form);
+// allocate + convert (syncs the primary stream); no-op when that form is built, drops the other form's block first
+int build_dense_prefilter(anrag_index *idx, int32_t form);
 void free_dense_prefilter(anrag_index *idx);
 struct DeferredTail;
 int launch_dense_prefilter_group(anrag_index *idx, hipStream_t stream, const float *const *d_queries, int32_t n_queries,

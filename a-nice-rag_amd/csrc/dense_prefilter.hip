@@ -259,6 +259,320 @@ __global__ __launch_bounds__(kScanThreads) void dense_prefilter_scan_kernel(
     }
 }
 
+// ---------------------------------------------------------------- K1F8: the same scan over an int8 shadow
+// DESIGN.md §3, "K1F8".  Row e: scale s_e and u = rint(e / s_e) in [-127, 127], e~ = s_e u (exact in fp64).  Query q
+// (per query, in the wave prologue): s_q, v likewise, q~ = s_q v.  The scan computes the integer S = v . u exactly
+// (|S| <= 2048 127^2 < 2^25, v_dot4_i32_i8 and an integer DPP tree) and a = fl(fl(S) fl(s_q s_e)), |a - q~.e~| <=
+// 2^-22 |a| + 2^-124 (three roundings of <= u each; the absolute part: subnormal s_q s_e or a).  With
+//   |s - q.e| <= gamma ||q|| ||e||,   q.e - q~.e~ = q.(e - e~) + (q - q~).e~
+// K1's score s lies in a +- (||q|| m1 + ||q - q~|| m2 + 2^-22 |a| + eta), m1 = ||e - e~|| + gamma ||e||, m2 = ||e~||.
+// m1, m2 (load time) and ||q||, ||q - q~|| (prologue) are fp64 sums rounded up to fp32; every fp32 step below is
+// pushed outward.  Non-finite and past-the-cap rows / queries get [-inf, +inf], as in K1F.
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void row_bounds_i8(float a, float m1, float m2, float qn, float eqn, float eta, float &lo,
+                                              float &hi) {
+    if (!(__builtin_isfinite(a) && __builtin_isfinite(m1) && __builtin_isfinite(m2) && __builtin_isfinite(qn) &&
+          __builtin_isfinite(eqn))) {
+        lo = -__builtin_huge_valf();
+        hi = __builtin_huge_valf();
+        return;
+    }
+    // three FMAs of non-negative terms (>= eta: normal), each within 2^-24 of its exact value: the sum is below
+    // r (1 - 2^-24)^-3; one more rounding of r (1 + 2^-21) stays above that.  Nothing overflows: every term < 2^122.
+    float r = __builtin_fmaf(qn, m1, eta);
+    r = __builtin_fmaf(eqn, m2, r);
+    r = __builtin_fmaf(__builtin_fabsf(a), 0x1p-22f, r);
+    r = __builtin_fmaf(r, 0x1p-21f, r);
+    const float h = a + r, l = a - r;
+    hi = __builtin_fmaf(__builtin_fabsf(h), 0x1p-22f, h);
+    lo = __builtin_fmaf(-__builtin_fabsf(l), 0x1p-22f, l);
+}
+
+// group_sum<G> of integers: the same DPP tree, exact
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ int32_t dpp_add_i32(int32_t v) {
+    return v + __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xF, false);
+}
+template <int G>
+__device__ __forceinline__ int32_t group_sum_i32(int32_t v) {
+    if constexpr (G >= 2) v = dpp_add_i32<0xB1, 0xF>(v);
+    if constexpr (G >= 4) v = dpp_add_i32<0x4E, 0xF>(v);
+    if constexpr (G >= 8) v = dpp_add_i32<0x141, 0xF>(v);
+    if constexpr (G >= 16) v = dpp_add_i32<0x140, 0xF>(v);
+    if constexpr (G >= 32) v = dpp_add_i32<0x142, 0xA>(v);
+    if constexpr (G >= 64) v = dpp_add_i32<0x143, 0xC>(v);
+    return v;
+}
+
+// x -> the int8 step count of scale s (NaN -> -127: such a query or row has an infinite radius anyway)
+__device__ __forceinline__ float quantise(float x, float inv_s) {
+    return __builtin_fminf(__builtin_fmaxf(__builtin_rintf(x * inv_s), -127.f), 127.f);
+}
+__device__ __forceinline__ uint32_t pack_i8(float y, int j) { return ((uint32_t)(int32_t)y & 0xFFu) << (8 * j); }
+
+// scale of a row or query: max|x| / 127 (any positive finite scale is correct: the radii are measured from the codes
+// actually stored); a zero, subnormal-to-nothing or non-finite maximum takes 1
+__device__ __forceinline__ float i8_scale(float mx) {
+    const float s = mx / 127.f;
+    return (s > 0.f && __builtin_isfinite(s)) ? s : 1.f;
+}
+
+// load time: one wave per row, 4 values per lane and step (dim % 256 == 0).  meta[row] = {s_e, m1, m2, 0}.
+__global__ __launch_bounds__(kScanThreads) void dense_prefilter_i8_convert_kernel(
+    const float *__restrict__ emb, int64_t n_rows, int32_t dim, uint32_t *__restrict__ img, f32x4 *__restrict__ meta) {
+    const int lane = lane_id();
+    const int64_t total_waves = (int64_t)gridDim.x * kScanWaves;
+    const double u = 0x1p-24, gamma = dim * u / (1.0 - dim * u);
+    for (int64_t row = (int64_t)blockIdx.x * kScanWaves + threadIdx.x / kWave; row < n_rows; row += total_waves) {
+        const f32x4 *p = reinterpret_cast<const f32x4 *>(emb + row * dim);
+        uint32_t *w = img + row * dim / 4;
+        float mx = 0.f;
+        double e2 = 0.0;
+        for (int c = lane; c < dim / 4; c += kWave) {
+            const f32x4 x = p[c];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                mx = __builtin_fmaxf(mx, __builtin_fabsf(x[j]));
+                e2 += (double)x[j] * (double)x[j];
+            }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            mx = __builtin_fmaxf(mx, __shfl_xor(mx, off, kWave));
+            e2 += __shfl_xor(e2, off, kWave);
+        }
+        const float s = i8_scale(mx), inv = 1.f / s;
+        double d2 = 0.0, t2 = 0.0;
+        for (int c = lane; c < dim / 4; c += kWave) {
+            const f32x4 x = p[c];
+            uint32_t b = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float y = quantise(x[j], inv);
+                const double t = (double)s * (double)y, d = (double)x[j] - t;  // s y: exact in fp64
+                d2 += d * d;
+                t2 += t * t;
+                b |= pack_i8(y, j);
+            }
+            w[c] = b;
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            d2 += __shfl_xor(d2, off, kWave);
+            t2 += __shfl_xor(t2, off, kWave);
+        }
+        if (lane == 0) {
+            const double ne = __builtin_sqrt(e2), nt = __builtin_sqrt(t2);
+            // fp64 sums of <= 2048 squares: relative error < 2^-40; widened by 2^-30, then rounded up to fp32
+            double m1 = (__builtin_sqrt(d2) + gamma * ne) * (1.0 + 0x1p-30), m2 = nt * (1.0 + 0x1p-30);
+            if (!(ne <= kRadiusCap) || !(nt <= kRadiusCap) || !__builtin_isfinite(m1)) m1 = __builtin_huge_val();
+            meta[row] = f32x4{s, __double2float_ru(m1), __double2float_ru(m2), 0.f};
+        }
+    }
+}
+
+// G, CH, R: the byte geometry of K1 for a row of dim bytes (scan_dispatch(dim / 4)): a lane's dwordx4 holds 16 codes,
+// elements 16 (c G + sub) .. +15 of the row.  Rows: a contiguous block per wave, as in the fp16 scan.  Per batch of RW
+// rows, lane j < RW also loads the metadata (and source id) of row base + j -- one coalesced load, issued with the
+// batch so that every batch issues the same loads -- and the RW integer sums are gathered to those lanes: bounds, hi
+// and the top-k offer are then computed once per batch for all its rows.
+// amdgpu_waves_per_eu(4): <= 128 VGPRs, so that K3's waves fit beside a scan wave on every SIMD (bm25.hip); the
+// unconstrained schedule of the 768-d shape took 133-136.
+template <int G, int CH, int R, bool FILTER>
+__global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(4))) void dense_prefilter_i8_scan_kernel(
+    const i32x4 *__restrict__ img, const f32x4 *__restrict__ meta, PrefilterQueries Q, int64_t n_rows, int32_t dim,
+    int32_t k, const uint16_t *__restrict__ src, const uint32_t *__restrict__ allow_bits) {
+    constexpr int GROUPS = kWave / G;
+    constexpr int RW = GROUPS * R;
+    static_assert(RW <= kWave, "a batch's rows fit the lanes of one wave");
+    constexpr int WAVES = kScanWaves;
+    __shared__ uint32_t lds_allow[FILTER ? 2048 : 1];
+
+    const int lane = lane_id();
+    const int wave = threadIdx.x / kWave;
+    const int sub = lane % G, grp = lane / G;
+    if constexpr (FILTER) {
+        for (int i = threadIdx.x; i < 2048; i += kScanThreads) lds_allow[i] = allow_bits[i];
+        __syncthreads();
+    }
+    const int64_t row_i4 = dim / 16;
+    const float eta = prefilter_eta(dim);
+    int32_t qv[CH][4];  // this lane's query codes, 4 per dword (the image's byte order)
+    float sq = 1.f, qn = 0.f, eqn = 0.f;
+    WaveTopK<float> top;
+    struct Batch {
+        i32x4 v[R][CH];
+        f32x4 m;  // {s_e, m1, m2, -} of row base + lane
+        uint32_t sid;
+    };
+    auto next_query = [&](int32_t qi) {
+        const f32x4 *__restrict__ query = reinterpret_cast<const f32x4 *>(Q.q[qi]);
+        double ss = 0.0;
+        float mx = 0.f;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            // one chunk (16 floats) in registers at a time, beside the batch in flight; the second pass reads the
+            // slice again (L2 hits) -- the fences keep the compiler from merging or hoisting the loads
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const f32x4 x = query[4 * (c * G + sub) + t];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    ss += (double)x[j] * (double)x[j];
+                    mx = __builtin_fmaxf(mx, __builtin_fabsf(x[j]));
+                }
+            }
+        }
+#pragma unroll
+        for (int off = 1; off < G; off <<= 1) {
+            ss += __shfl_xor(ss, off, kWave);
+            mx = __builtin_fmaxf(mx, __shfl_xor(mx, off, kWave));
+        }
+        sq = i8_scale(mx);
+        const float inv = 1.f / sq;
+        double d2 = 0.0;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const f32x4 x = query[4 * (c * G + sub) + t];
+                uint32_t b = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float y = quantise(x[j], inv);
+                    const double d = (double)x[j] - (double)sq * (double)y;
+                    d2 += d * d;
+                    b |= pack_i8(y, j);
+                }
+                qv[c][t] = (int32_t)b;
+            }
+        }
+#pragma unroll
+        for (int off = 1; off < G; off <<= 1) d2 += __shfl_xor(d2, off, kWave);
+        const double nq = __builtin_sqrt(ss) * (1.0 + 0x1p-30), ne = __builtin_sqrt(d2) * (1.0 + 0x1p-30);
+        qn = nq <= kRadiusCap ? __double2float_ru(nq) : __builtin_huge_valf();  // NaN / inf / huge: +inf
+        eqn = ne <= kRadiusCap ? __double2float_ru(ne) : __builtin_huge_valf();
+        sq = read_lane(sq, 0);  // equal in every lane: held in SGPRs
+        qn = read_lane(qn, 0);
+        eqn = read_lane(eqn, 0);
+        top.init(k);
+    };
+    const int64_t total_waves = (int64_t)gridDim.x * WAVES;
+    const int64_t wave_global = (int64_t)blockIdx.x * WAVES + wave;
+    const int64_t rows_per_wave = ((n_rows + total_waves - 1) / total_waves + RW - 1) / RW * RW;
+    const int64_t base0 = wave_global * rows_per_wave;
+    const int64_t lim = base0 + rows_per_wave < n_rows ? base0 + rows_per_wave : n_rows;
+    float hb = 0.f;  // lane j <- hi of row hbase + j
+    int64_t hbase = base0;
+    int32_t qi = 0;
+    auto flush = [&](int32_t qe) {
+        Q.blk_s[qe][(blockIdx.x * WAVES + wave) * kListLen + lane] = top.s;
+        Q.blk_r[qe][(blockIdx.x * WAVES + wave) * kListLen + lane] = top.r;
+        if (hbase + lane < lim) Q.hi[qe][hbase + lane] = hb;
+        hbase = base0;
+    };
+    // addresses: a wave-uniform 64-bit base and 32-bit lane offsets (rows past the end clamp to the last row)
+    auto issue = [&](int64_t base, Batch &bt) {
+        const int64_t left = n_rows - 1 - base;  // >= 0: base < n_rows
+        const int32_t last = left < RW ? (int32_t)left : RW;
+        const i32x4 *pb = img + base * row_i4;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int32_t o = r * GROUPS + grp;
+            const i32x4 *p = pb + (int32_t)((o < last ? o : last) * (int32_t)row_i4 + sub);
+#pragma unroll
+            for (int c = 0; c < CH; ++c) bt.v[r][c] = __builtin_nontemporal_load(p + c * G);
+        }
+        const int32_t mo = lane < RW ? lane : RW - 1;
+        const int32_t mc = mo < last ? mo : last;
+        const float *pm = reinterpret_cast<const float *>(meta + base) + 4 * mc;  // one dwordx3: the fourth is padding
+        bt.m = f32x4{pm[0], pm[1], pm[2], 0.f};
+        if constexpr (FILTER) bt.sid = src[base + mc];
+    };
+    auto reduce = [&](int64_t base, const Batch &bt) {
+        int32_t sum = 0;  // lane j < RW: v . u of row base + j
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            int32_t acc = 0;
+#pragma unroll
+            for (int c = 0; c < CH; ++c)
+#pragma unroll
+                for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_sdot4(bt.v[r][c][t], qv[c][t], acc, false);
+            acc = group_sum_i32<G>(acc);
+#pragma unroll
+            for (int g = 0; g < GROUPS; ++g) {
+                const int32_t sg = (int32_t)read_lane((uint32_t)acc, g * G + G - 1);
+                sum = lane == r * GROUPS + g ? sg : sum;
+            }
+        }
+        const int64_t row = base + lane;
+        bool ok = lane < RW && row < lim;
+        if constexpr (FILTER) ok = ok && source_ok(lds_allow, bt.sid);
+        const float a = (float)sum * (sq * bt.m.x);
+        float lo, hi;
+        row_bounds_i8(a, bt.m.y, bt.m.z, qn, eqn, eta, lo, hi);
+        const float hv = ok ? hi : __builtin_nanf("");
+        // rows base .. base + RW - 1 take slots off .. off + RW - 1 of the 64-row store, the overflow the next one's
+        const int off = (int)(base - hbase);
+        const float sh = __shfl(hv, (lane - off) & (kWave - 1), kWave);
+        if (lane >= off && lane < off + RW) hb = sh;
+        if (off + RW >= kWave) {
+            if (hbase + lane < lim) Q.hi[qi][hbase + lane] = hb;
+            hbase += kWave;
+            if (lane < off + RW - kWave) hb = sh;
+        }
+        const uint32_t r32 = (uint32_t)row;
+        top.offer_lanes(ok && top.admits(lo, r32), lo, r32);
+    };
+    if (base0 >= n_rows) {  // a wave without rows (tiny corpora): empty lists
+        top.init(1);
+        for (int32_t qe = 0; qe < Q.n; ++qe) {
+            Q.blk_s[qe][(blockIdx.x * WAVES + wave) * kListLen + lane] = top.s;
+            Q.blk_r[qe][(blockIdx.x * WAVES + wave) * kListLen + lane] = top.r;
+        }
+        return;
+    }
+    Batch b0, b1;
+    issue(base0, b0);  // in flight during the first prologue
+    next_query(0);
+    int64_t base = base0;
+    // K1's loop: the next batch is issued unconditionally before the current one is reduced (dense_scan.hip)
+    for (;;) {
+        int32_t nq = qi;
+        int64_t next = base + RW;
+        if (next >= lim) {
+            next = base0;
+            ++nq;
+        }
+        issue(next, b1);
+        reduce(base, b0);
+        if (nq != qi) {
+            flush(qi);
+            if (nq >= Q.n) break;
+            qi = nq;
+            next_query(qi);
+        }
+        base = next;
+        next = base + RW;
+        if (next >= lim) {
+            next = base0;
+            ++nq;
+        }
+        issue(next, b0);
+        reduce(base, b1);
+        if (nq != qi) {
+            flush(qi);
+            if (nq >= Q.n) break;
+            qi = nq;
+            next_query(qi);
+        }
+        base = next;
+    }
+}
+
 // ---------------------------------------------------------------- 2. T per query: one workgroup of 16 waves each
 constexpr int kThrWaves = 16;
 __global__ __launch_bounds__(kThrWaves * kWave) void dense_prefilter_threshold_kernel(PrefilterQueries Q, int32_t n_lists,
@@ -357,37 +671,42 @@ __global__ __launch_bounds__(kScanThreads) void dense_prefilter_rescore_kernel(
 }
 
 // ---------------------------------------------------------------- host
-// The dimensions served: the fp16 row of dim values has K1's byte geometry of a dim / 2 row (Half), shapes of up to 4
-// dwordx4 per lane and row (dim <= 2,048); the rescore kernel takes K1's own shape for dim (Full).  An explicit table, so
-// that only the kernels these six dimensions run are compiled.
-template <class H, class F32>
+// The dimensions served: the fp16 row of dim values has K1's byte geometry of a dim / 2 row (Half), the int8 row that of
+// a dim / 4 row (Quarter), shapes of up to 4 dwordx4 per lane and row (dim <= 2,048); the rescore kernel takes K1's own
+// shape for dim (Full).  An explicit table, so that only the kernels these six dimensions run are compiled.
+template <class H, class Q4, class F32>
 struct PrefilterShape {
     using Half = H;
+    using Quarter = Q4;
     using Full = F32;
 };
 template <class F>
 static bool prefilter_dispatch(int d, F &&f) {
     switch (d) {
-        case 256: f(PrefilterShape<ScanShape<32, 1>, ScanShape<32, 2>>{}); return true;
-        case 512: f(PrefilterShape<ScanShape<32, 2>, ScanShape<64, 2>>{}); return true;
-        case 768: f(PrefilterShape<ScanShape<32, 3>, ScanShape<64, 3>>{}); return true;
-        case 1024: f(PrefilterShape<ScanShape<64, 2>, ScanShape<64, 4>>{}); return true;
-        case 1536: f(PrefilterShape<ScanShape<64, 3>, ScanShape<64, 6>>{}); return true;
-        case 2048: f(PrefilterShape<ScanShape<64, 4>, ScanShape<64, 8>>{}); return true;
+        case 256: f(PrefilterShape<ScanShape<32, 1>, ScanShape<16, 1>, ScanShape<32, 2>>{}); return true;
+        case 512: f(PrefilterShape<ScanShape<32, 2>, ScanShape<32, 1>, ScanShape<64, 2>>{}); return true;
+        case 768: f(PrefilterShape<ScanShape<32, 3>, ScanShape<16, 3>, ScanShape<64, 3>>{}); return true;
+        case 1024: f(PrefilterShape<ScanShape<64, 2>, ScanShape<32, 2>, ScanShape<64, 4>>{}); return true;
+        case 1536: f(PrefilterShape<ScanShape<64, 3>, ScanShape<32, 3>, ScanShape<64, 6>>{}); return true;
+        case 2048: f(PrefilterShape<ScanShape<64, 4>, ScanShape<64, 2>, ScanShape<64, 8>>{}); return true;
         default: return false;
     }
 }
 
-// ... and the table agrees with scan_dispatch: Half is the shape of dim / 2, Full (the bits of K1's score) that of dim
+// ... and the table agrees with scan_dispatch: Half is the shape of dim / 2, Quarter that of dim / 4, Full (the bits of
+// K1's score) that of dim
 bool dense_prefilter_has_shape(const anrag_index *idx) {
     const int d = idx->dim;
     bool ok = false;
     prefilter_dispatch(d, [&](auto ps) {
         using P = decltype(ps);
-        bool half = false, full = false;
+        bool half = false, quarter = false, full = false;
         scan_dispatch(d / 2, [&](auto s) { half = decltype(s)::kG == P::Half::kG && decltype(s)::kCH == P::Half::kCH; });
+        scan_dispatch(d / 4, [&](auto s) {
+            quarter = decltype(s)::kG == P::Quarter::kG && decltype(s)::kCH == P::Quarter::kCH;
+        });
         scan_dispatch(d, [&](auto s) { full = decltype(s)::kG == P::Full::kG && decltype(s)::kCH == P::Full::kCH; });
-        ok = half && full;
+        ok = half && quarter && full;
     });
     return ok;
 }
@@ -400,17 +719,28 @@ int dense_prefilter_vgprs(const anrag_index *idx) {
     };
     prefilter_dispatch(idx->dim, [&](auto ps) {
         using H = typename decltype(ps)::Half;
+        using Q4 = typename decltype(ps)::Quarter;
         using F = typename decltype(ps)::Full;
-        take(reinterpret_cast<const void *>(&dense_prefilter_scan_kernel<H::kG, H::kCH, H::kR, true>));
+        if (idx->pf_form == kPrefilterInt8)
+            take(reinterpret_cast<const void *>(&dense_prefilter_i8_scan_kernel<Q4::kG, Q4::kCH, Q4::kR, true>));
+        else
+            take(reinterpret_cast<const void *>(&dense_prefilter_scan_kernel<H::kG, H::kCH, H::kR, true>));
         take(reinterpret_cast<const void *>(&dense_prefilter_rescore_kernel<F::kG, F::kCH>));
     });
     return regs;
 }
 
-int64_t dense_prefilter_bytes(int64_t n_rows, int32_t dim) {
+// one block per form: the image and its per-row data (fp16: the radius m; int8: {s_e, m1, m2, 0}), then what both
+// forms share -- hi per list set, T, the survivor count
+int64_t dense_prefilter_bytes(int64_t n_rows, int32_t dim, int32_t form) {
     Carver c(nullptr);
-    c.take<_Float16>(n_rows * dim);
-    c.take<float>(n_rows);
+    if (form == kPrefilterInt8) {
+        c.take<int8_t>(n_rows * dim);
+        c.take<float>(4 * n_rows);
+    } else {
+        c.take<_Float16>(n_rows * dim);
+        c.take<float>(n_rows);
+    }
     c.take<float>((int64_t)kPipeSlots * ((n_rows + 63) / 64 * 64));
     c.take<float>(kPipeSlots);
     c.take<unsigned long long>(1);
@@ -424,15 +754,17 @@ void free_dense_prefilter(anrag_index *idx) {
     }
     idx->pf_block = nullptr;
     idx->pf_bytes = 0;
+    idx->pf_form = 0;
     idx->d_pf_img = nullptr;
     idx->d_pf_m = idx->d_pf_hi = idx->d_pf_thr = nullptr;
     idx->d_pf_survivors = nullptr;
 }
 
-int build_dense_prefilter(anrag_index *idx) {
-    if (idx->pf_block) return ANRAG_OK;
+int build_dense_prefilter(anrag_index *idx, int32_t form) {
+    if (idx->pf_block && idx->pf_form == form) return ANRAG_OK;
     ANRAG_REQUIRE(dense_prefilter_has_shape(idx), "dense prefilter: no kernel shape for dim %d", idx->dim);
-    const int64_t n = idx->n_rows, bytes = dense_prefilter_bytes(n, idx->dim);
+    free_dense_prefilter(idx);  // the other form's block: one at a time
+    const int64_t n = idx->n_rows, bytes = dense_prefilter_bytes(n, idx->dim, form);
     void *p = nullptr;
     hipError_t e = counted_malloc(&p, (size_t)bytes);
     if (e != hipSuccess) {
@@ -442,10 +774,16 @@ int build_dense_prefilter(anrag_index *idx) {
     }
     idx->pf_block = p;
     idx->pf_bytes = bytes;
+    idx->pf_form = form;
     idx->hbm_bytes += bytes;
     Carver c(static_cast<char *>(p));
-    idx->d_pf_img = c.take<_Float16>(n * idx->dim);
-    idx->d_pf_m = c.take<float>(n);
+    if (form == kPrefilterInt8) {
+        idx->d_pf_img = c.take<int8_t>(n * idx->dim);
+        idx->d_pf_m = c.take<float>(4 * n);
+    } else {
+        idx->d_pf_img = c.take<_Float16>(n * idx->dim);
+        idx->d_pf_m = c.take<float>(n);
+    }
     idx->pf_hi_stride = (n + 63) / 64 * 64;
     idx->d_pf_hi = c.take<float>((int64_t)kPipeSlots * idx->pf_hi_stride);
     idx->d_pf_thr = c.take<float>(kPipeSlots);
@@ -454,8 +792,13 @@ int build_dense_prefilter(anrag_index *idx) {
     ANRAG_HIP(hipMemsetAsync(idx->d_pf_survivors, 0, sizeof(unsigned long long), st));
     const int64_t need = (n + kScanWaves - 1) / kScanWaves;
     const int64_t cap = (int64_t)idx->n_cus * 8;
-    dense_prefilter_convert_kernel<<<(unsigned)(need < cap ? need : cap), kScanThreads, 0, st>>>(
-        idx->d_emb, n, idx->dim, static_cast<_Float16 *>(idx->d_pf_img), idx->d_pf_m);
+    const unsigned grid = (unsigned)(need < cap ? need : cap);
+    if (form == kPrefilterInt8)
+        dense_prefilter_i8_convert_kernel<<<grid, kScanThreads, 0, st>>>(
+            idx->d_emb, n, idx->dim, static_cast<uint32_t *>(idx->d_pf_img), reinterpret_cast<f32x4 *>(idx->d_pf_m));
+    else
+        dense_prefilter_convert_kernel<<<grid, kScanThreads, 0, st>>>(idx->d_emb, n, idx->dim,
+                                                                     static_cast<_Float16 *>(idx->d_pf_img), idx->d_pf_m);
     ANRAG_HIP(hipGetLastError());
     ANRAG_HIP(hipStreamSynchronize(st));
     idx->pf_queries = 0;
@@ -475,17 +818,29 @@ int launch_dense_prefilter_group(anrag_index *idx, hipStream_t st, const float *
         Q.thr[i] = idx->d_pf_thr + sets[j];
     }
     const int grid = dense_scan_grid(idx);
-    const f32x4 *img = reinterpret_cast<const f32x4 *>(idx->d_pf_img);
     hipError_t err = hipSuccess;  // of the first launch that failed
     prefilter_dispatch(idx->dim, [&](auto ps) {
         using H = typename decltype(ps)::Half;
+        using Q4 = typename decltype(ps)::Quarter;
         using F = typename decltype(ps)::Full;
-        if (allow)
-            dense_prefilter_scan_kernel<H::kG, H::kCH, H::kR, true><<<grid, kScanThreads, 0, st>>>(
-                img, idx->d_pf_m, Q, idx->n_rows, idx->dim, k, idx->d_dense_src, allow);
-        else
-            dense_prefilter_scan_kernel<H::kG, H::kCH, H::kR, false><<<grid, kScanThreads, 0, st>>>(
-                img, idx->d_pf_m, Q, idx->n_rows, idx->dim, k, nullptr, nullptr);
+        if (idx->pf_form == kPrefilterInt8) {
+            const i32x4 *img = reinterpret_cast<const i32x4 *>(idx->d_pf_img);
+            const f32x4 *meta = reinterpret_cast<const f32x4 *>(idx->d_pf_m);
+            if (allow)
+                dense_prefilter_i8_scan_kernel<Q4::kG, Q4::kCH, Q4::kR, true><<<grid, kScanThreads, 0, st>>>(
+                    img, meta, Q, idx->n_rows, idx->dim, k, idx->d_dense_src, allow);
+            else
+                dense_prefilter_i8_scan_kernel<Q4::kG, Q4::kCH, Q4::kR, false><<<grid, kScanThreads, 0, st>>>(
+                    img, meta, Q, idx->n_rows, idx->dim, k, nullptr, nullptr);
+        } else {
+            const f32x4 *img = reinterpret_cast<const f32x4 *>(idx->d_pf_img);
+            if (allow)
+                dense_prefilter_scan_kernel<H::kG, H::kCH, H::kR, true><<<grid, kScanThreads, 0, st>>>(
+                    img, idx->d_pf_m, Q, idx->n_rows, idx->dim, k, idx->d_dense_src, allow);
+            else
+                dense_prefilter_scan_kernel<H::kG, H::kCH, H::kR, false><<<grid, kScanThreads, 0, st>>>(
+                    img, idx->d_pf_m, Q, idx->n_rows, idx->dim, k, nullptr, nullptr);
+        }
         if ((err = hipGetLastError()) != hipSuccess) return;
         dense_prefilter_threshold_kernel<<<n_queries, kThrWaves * kWave, 0, st>>>(Q, grid * kScanWaves, k);
         if ((err = hipGetLastError()) != hipSuccess) return;

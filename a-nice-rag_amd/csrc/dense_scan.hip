@@ -435,7 +435,7 @@ int launch_dense_scan_group(anrag_index *idx, hipStream_t st, const float *const
     const int d = idx->dim;
     const int grid = dense_scan_grid(idx);
     const uint32_t *allow = (idx->d_dense_src != nullptr) ? d_allow_bits : nullptr;
-    if (!d_scores_out && k >= 1 && k <= kListLen && idx->pf_on) {  // K1F: fp16 shadow scan + exact rescoring (same lists)
+    if (!d_scores_out && k >= 1 && k <= kListLen && idx->pf_on) {  // K1F / K1F8: shadow scan + exact rescoring (same lists)
         LaunchTimer t(idx, ANRAG_KERNEL_DENSE_SCAN, st, n_queries);
         return launch_dense_prefilter_group(idx, st, d_queries, n_queries, k, allow, sets, dt);
     }

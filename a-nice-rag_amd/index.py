@@ -209,12 +209,12 @@ class Index:
         nat.check(self._lib.anrag_set_batched_precision(self.handle, {"f32": 0, "bf16x3": 1}[mode]))
 
     def set_dense_prefilter(self, mode: int = -1) -> None:
-        """Dense top-k route: -1 auto (on past 1 GiB of fp32 corpus), 0 the fp32 scan, 1 the fp16 prefilter + exact
-        rescoring.  Results are bit-identical either way."""
+        """Dense top-k route: -1 auto (the int8 prefilter past 1 GiB of fp32 corpus), 0 the fp32 scan, 1 the fp16
+        prefilter + exact rescoring, 2 the int8 prefilter + exact rescoring.  Results are bit-identical in every mode."""
         nat.check(self._lib.anrag_set_dense_prefilter(self.handle, int(mode)))
 
     def dense_prefilter_stats(self) -> tuple:
-        """(queries answered through the prefilter, rows rescored) since it was built."""
+        """(queries answered through the prefilter, rows rescored) since its current form was built."""
         q, s = C.c_int64(0), C.c_int64(0)
         nat.check(self._lib.anrag_dense_prefilter_stats(self.handle, C.byref(q), C.byref(s)))
         return q.value, s.value

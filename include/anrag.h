@@ -194,19 +194,23 @@ int anrag_dense_search_batch_device(anrag_index *idx, const float *d_queries, in
 int anrag_set_batched_precision(anrag_index *idx, int32_t mode);
 
 /* Route of the dense top-k leg (k <= ANRAG_FUSED_K_MAX, every entry point that keeps lists: single, grouped, hybrid,
- * sharded).  The results do not depend on it: ids and fp32 scores are bit-identical either way.
- * 0: the fp32 scan.  1: the prefilter -- an fp16 copy of the corpus is scanned, rows that provably cannot reach the
- * top k are dropped, and the few left are rescored with the fp32 scan's own arithmetic (half the bytes per query).
- * -1 (default): on when the fp32 corpus is larger than 1 GiB and the dimension has a kernel shape (a multiple of 256
- * up to 2,048); when it cannot allocate it silently stays on the fp32 scan, where mode 1 returns ANRAG_ERR_NOMEM.
- * MEMORY: n_rows * (2 * dim + 4) bytes for the fp16 copy and the per-row error radii, plus 4 * n_rows bytes per
- * pipeline slot (32) for the rows' score bounds; counted in anrag_index_info's hbm_bytes, built by the first load or
- * call that turns it on, dropped by the next anrag_dense_load / anrag_index_destroy (not by switching to mode 0).
- * The environment variable ANRAG_DENSE_PREFILTER=0|1, read at anrag_index_create, sets the initial mode. */
+ * sharded).  The results do not depend on it: ids and fp32 scores are bit-identical in every mode.
+ * 0: the fp32 scan.  1: the fp16 prefilter -- an fp16 copy of the corpus is scanned, rows that provably cannot reach
+ * the top k are dropped, and the few left are rescored with the fp32 scan's own arithmetic (half the bytes per query).
+ * 2: the int8 prefilter -- the same with an int8 copy and one scale per row (a quarter of the bytes per query).
+ * -1 (default): the int8 prefilter when the fp32 corpus is larger than 1 GiB and the dimension has a kernel shape (a
+ * multiple of 256 up to 2,048); when it cannot allocate it silently stays on the fp32 scan, where modes 1 and 2 return
+ * ANRAG_ERR_NOMEM.
+ * MEMORY: mode 1 n_rows * (2 * dim + 4) bytes for the fp16 copy and the per-row error radii; mode 2 n_rows * (dim + 16)
+ * bytes for the int8 copy and the per-row scale and radii; either plus 4 * n_rows bytes per pipeline slot (32) for the
+ * rows' score bounds.  One form is held at a time (switching between 1 and 2 replaces it); counted in
+ * anrag_index_info's hbm_bytes, built by the first load or call that turns it on, dropped by the next
+ * anrag_dense_load / anrag_index_destroy (not by switching to mode 0).
+ * The environment variable ANRAG_DENSE_PREFILTER=0|1|2, read at anrag_index_create, sets the initial mode. */
 int anrag_set_dense_prefilter(anrag_index *idx, int32_t mode);
 
-/* Cumulative counters of the prefilter since it was built: queries it answered and rows it rescored (waits for the
- * index's streams). */
+/* Cumulative counters of the prefilter since its current form was built: queries it answered and rows it rescored
+ * (waits for the index's streams). */
 int anrag_dense_prefilter_stats(anrag_index *idx, int64_t *queries, int64_t *survivors);
 
 /* All N scores of one query (what search_engine.py:81 materialises), for tests
