@@ -888,16 +888,30 @@ int anrag_wrrf_device(anrag_index *idx, const anrag_candidate *d_dense, int32_t 
 }
 
 // ------------------------------------------------------------------ fused hybrid query
-// One hybrid query through the stream pipeline, THREE launches:
-//   primary    K1 scan                      -> dense block lists of the query's slot
-//   secondary  K3 BM25                      -> BM25 partition lists of the slot
-//   tail       (fused: secondary; candidates: fusion stream) waits for the scan, then ONE kernel merges both
-//              list sets and either fuses (WRRF + top-n -> d_out) or writes both candidate lists to d_out
+// One hybrid query through the stream pipeline.  T is the tail's stream: `secondary` when fusing, `fusion` for candidates.
+//   primary    the scan: K1, or the shadow scan of K1F / K1F8       -> dense block lists (K1F: hi and lo lists) of the slot
+//   secondary  K3 BM25                                              -> BM25 partition lists of the slot
+//   T          waits for the scan, then [K1F: threshold, rescore -> the slot's exact lists, then] ONE tail kernel merges
+//              both list sets and either fuses (WRRF + top-n -> d_out) or writes both candidate lists to d_out
+// Three launches per query with K1, five with the prefilter.
+//
+//   primary    | scan i        | scan i+1          | scan i+2          |
+//   secondary  | bm25 i |      | bm25 i+1 | thr i, rescore i, tail i   | bm25 i+2 | thr i+1, ...      (fused: T = secondary)
+//
 // slot = sequence number % kPipeSlots.  Back-to-back queries keep the scans adjacent on `primary` with NO
 // event wait between them (a barrier packet in front of every scan cost 5-6 us per query on MI355X); everything
-// else of query i runs under the scans of the following queries.  The only backpressure is on the host: before
-// a slot is reused the call waits until the tail that last read it has finished, so at most kPipeSlots queries
-// are in flight and the device never has to be told to wait for a buffer.
+// else of query i runs under the scans of the following queries: `primary` carries nothing but scans, so that HBM is
+// never left idle for a one-workgroup threshold kernel.  ev_scan is recorded right behind the scan launch.  The only
+// backpressure is on the host: before a slot is reused the call waits until the tail that last read it has finished,
+// so at most kPipeSlots queries are in flight and the device never has to be told to wait for a buffer.
+// Slot lifetimes with the prefilter: hi[slot], T[slot] and the slot's lists are written by scan i on `primary` and then
+// read and rewritten by threshold i, rescore i and tail i on T, in stream order behind T's wait for ev_scan.  ev_fused[slot]
+// is recorded on T behind the tail, hence behind the rescore too, and the host waits for it before it launches the scan
+// of query i + kPipeSlots: the next writer of anything the slot owns starts after its last reader has ended, in both tail
+// modes.  A group records ONE ev_scan behind its one scan launch and every member's ev_fused behind the group's one
+// tail launch, which follows the group's one threshold and one rescore launch on T: the same argument per member.
+// Whoever frees or rebuilds the prefilter block, changes the route or hands the list sets to the lanes goes through
+// sync_all first, which waits for all three streams, T included.
 // A GROUP of n <= kScanGroupMax queries takes n consecutive slots and ONE scan launch (dense_scan.hip: each query
 // is still its own pass over the matrix; a workgroup moves on to the next query without a grid-wide step, so the
 // launch gap, the ramp and the spread of finishing times are paid once per launch): worth +10-14 % at the shard
@@ -933,7 +947,8 @@ static int hybrid_enqueue_group(anrag_index *idx, TailMode tail, const GroupQuer
     idx->hyb_outstanding = true;
     int rc;
     if (use_dense) {
-        if ((rc = launch_dense_scan_group(idx, P, qs, n, k, d_allow_dense, nullptr, slot))) return rc;
+        if ((rc = launch_dense_scan_group(idx, P, qs, n, k, d_allow_dense, nullptr, slot, 0, nullptr, /*finish_later*/ true)))
+            return rc;
         ANRAG_HIP(hipEventRecord(idx->ev_scan[slot[0]], P));
     }
     hipStream_t T = tail == kTailFuse ? S : F;
@@ -957,7 +972,10 @@ static int hybrid_enqueue_group(anrag_index *idx, TailMode tail, const GroupQuer
             ANRAG_HIP(hipStreamWaitEvent(T, idx->ev_bm25[slot[0]], 0));
         }
     }
-    if (use_dense) ANRAG_HIP(hipStreamWaitEvent(T, idx->ev_scan[slot[0]], 0));
+    if (use_dense) {
+        ANRAG_HIP(hipStreamWaitEvent(T, idx->ev_scan[slot[0]], 0));
+        if ((rc = launch_dense_scan_finish(idx, T, qs, n, k, slot))) return rc;  // K1F: threshold + rescore, off `primary`
+    }
     {  // the group's tails: one launch, a workgroup per query
         anrag_candidate *outs[kScanGroupMax];
         int32_t *counts[kScanGroupMax];

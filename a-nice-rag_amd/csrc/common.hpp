@@ -312,11 +312,20 @@ int64_t dense_prefilter_bytes(int64_t n_rows, int32_t dim, int32_t form);
 int build_dense_prefilter(anrag_index *idx, int32_t form);
 void free_dense_prefilter(anrag_index *idx);
 struct DeferredTail;
-int launch_dense_prefilter_group(anrag_index *idx, hipStream_t stream, const float *const *d_queries, int32_t n_queries,
-                                 int32_t k, const uint32_t *d_allow_bits, const int *sets, const DeferredTail &dt);
+// the scan half (hi, lo lists) and the finish half (threshold + rescore -> the set's exact lists; a lane's DeferredTail
+// rides in the rescore launch).  One stream for both, or the finish half on another stream behind an event recorded
+// after the scan half: the hybrid pipeline keeps `primary` for the scans alone that way.
+int launch_dense_prefilter_scan(anrag_index *idx, hipStream_t stream, const float *const *d_queries, int32_t n_queries,
+                                int32_t k, const uint32_t *d_allow_bits, const int *sets);
+int launch_dense_prefilter_finish(anrag_index *idx, hipStream_t stream, const float *const *d_queries, int32_t n_queries,
+                                  int32_t k, const int *sets, const DeferredTail &dt);
+// `finish_later`: when the top-k goes through the prefilter, launch its scan half only; the caller then orders
+// launch_dense_scan_finish (same queries, k and sets; a no-op on every other route) behind it on a stream of its choice.
 int launch_dense_scan_group(anrag_index *idx, hipStream_t stream, const float *const *d_queries, int32_t n_queries,
                             int32_t k, const uint32_t *d_allow_bits, float *d_scores_out, const int *sets,
-                            int64_t scores_stride = 0, const PendingTail *pending = nullptr);
+                            int64_t scores_stride = 0, const PendingTail *pending = nullptr, bool finish_later = false);
+int launch_dense_scan_finish(anrag_index *idx, hipStream_t stream, const float *const *d_queries, int32_t n_queries,
+                             int32_t k, const int *sets);
 int launch_bm25_lists(anrag_index *idx, hipStream_t st, const int32_t *d_terms, int32_t n_terms, int32_t k,
                       const uint32_t *d_allow_bits, double *d_scores_out, int set);
 int launch_bm25_lists_group(anrag_index *idx, hipStream_t st, const int32_t *const *d_terms, const int32_t *n_terms,

@@ -805,8 +805,12 @@ int build_dense_prefilter(anrag_index *idx, int32_t form) {
     return ANRAG_OK;
 }
 
-int launch_dense_prefilter_group(anrag_index *idx, hipStream_t st, const float *const *d_queries, int32_t n_queries,
-                                 int32_t k, const uint32_t *allow, const int *sets, const DeferredTail &dt) {
+// The three launches come in two halves so that the hybrid pipeline can keep `primary` for the scans alone: the scan
+// half writes hi[set] and the lo lists of the set; the finish half (threshold, rescore) reads them, the query vectors and
+// the fp32 rows, and leaves the set's exact lists.  Everything the finish half touches is the set's own (hi row, T,
+// lists), so it may run on another stream, behind an event recorded after the scan half, while later scans proceed.
+static PrefilterQueries prefilter_queries(const anrag_index *idx, const float *const *d_queries, int32_t n_queries,
+                                          const int *sets) {
     PrefilterQueries Q;
     Q.n = n_queries;
     for (int i = 0; i < kScanGroupMax; ++i) {
@@ -817,12 +821,16 @@ int launch_dense_prefilter_group(anrag_index *idx, hipStream_t st, const float *
         Q.blk_r[i] = idx->d_blk_row_a + (int64_t)sets[j] * kMaxScanLists * kListLen;
         Q.thr[i] = idx->d_pf_thr + sets[j];
     }
+    return Q;
+}
+
+int launch_dense_prefilter_scan(anrag_index *idx, hipStream_t st, const float *const *d_queries, int32_t n_queries,
+                                int32_t k, const uint32_t *allow, const int *sets) {
+    const PrefilterQueries Q = prefilter_queries(idx, d_queries, n_queries, sets);
     const int grid = dense_scan_grid(idx);
-    hipError_t err = hipSuccess;  // of the first launch that failed
     prefilter_dispatch(idx->dim, [&](auto ps) {
         using H = typename decltype(ps)::Half;
         using Q4 = typename decltype(ps)::Quarter;
-        using F = typename decltype(ps)::Full;
         if (idx->pf_form == kPrefilterInt8) {
             const i32x4 *img = reinterpret_cast<const i32x4 *>(idx->d_pf_img);
             const f32x4 *meta = reinterpret_cast<const f32x4 *>(idx->d_pf_m);
@@ -841,7 +849,19 @@ int launch_dense_prefilter_group(anrag_index *idx, hipStream_t st, const float *
                 dense_prefilter_scan_kernel<H::kG, H::kCH, H::kR, false><<<grid, kScanThreads, 0, st>>>(
                     img, idx->d_pf_m, Q, idx->n_rows, idx->dim, k, nullptr, nullptr);
         }
-        if ((err = hipGetLastError()) != hipSuccess) return;
+    });
+    ANRAG_HIP(hipGetLastError());
+    idx->pf_queries += n_queries;
+    return ANRAG_OK;
+}
+
+int launch_dense_prefilter_finish(anrag_index *idx, hipStream_t st, const float *const *d_queries, int32_t n_queries,
+                                  int32_t k, const int *sets, const DeferredTail &dt) {
+    const PrefilterQueries Q = prefilter_queries(idx, d_queries, n_queries, sets);
+    const int grid = dense_scan_grid(idx);
+    hipError_t err = hipSuccess;  // of the first launch that failed
+    prefilter_dispatch(idx->dim, [&](auto ps) {
+        using F = typename decltype(ps)::Full;
         dense_prefilter_threshold_kernel<<<n_queries, kThrWaves * kWave, 0, st>>>(Q, grid * kScanWaves, k);
         if ((err = hipGetLastError()) != hipSuccess) return;
         dense_prefilter_rescore_kernel<F::kG, F::kCH><<<grid + (dt.out ? 1 : 0), kScanThreads, 0, st>>>(
@@ -849,7 +869,6 @@ int launch_dense_prefilter_group(anrag_index *idx, hipStream_t st, const float *
         err = hipGetLastError();
     });
     ANRAG_HIP(err);
-    idx->pf_queries += n_queries;
     return ANRAG_OK;
 }
 

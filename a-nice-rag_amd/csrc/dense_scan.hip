@@ -404,11 +404,20 @@ bool dense_scan_has_shape(const anrag_index *idx) {
     return scan_dispatch(idx->dim, [](auto) {});
 }
 
+static bool prefilter_serves(const anrag_index *idx, int32_t k) { return k >= 1 && k <= kListLen && idx->pf_on; }
+
+int launch_dense_scan_finish(anrag_index *idx, hipStream_t st, const float *const *d_queries, int32_t n_queries, int32_t k,
+                             const int *sets) {
+    if (!prefilter_serves(idx, k)) return ANRAG_OK;  // K1 left the exact lists itself
+    return launch_dense_prefilter_finish(idx, st, d_queries, n_queries, k, sets, DeferredTail{});
+}
+
 int launch_dense_scan_group(anrag_index *idx, hipStream_t st, const float *const *d_queries, int32_t n_queries, int32_t k,
                             const uint32_t *d_allow_bits, float *d_scores_out, const int *sets, int64_t scores_stride,
-                            const PendingTail *pending) {
+                            const PendingTail *pending, bool finish_later) {
     ANRAG_REQUIRE(n_queries >= 1 && n_queries <= kScanGroupMax, "scan group of %d queries", n_queries);
     ANRAG_REQUIRE(!pending || (!d_scores_out && dense_scan_has_shape(idx)), "deferred list merge: shaped scan kernels only");
+    ANRAG_REQUIRE(!finish_later || (!pending && !d_scores_out), "a split scan carries no deferred merge and no score rows");
     DeferredTail dt{};
     if (pending) {
         dt.blk_s = idx->d_blk_score_f32 + (int64_t)pending->set * kMaxScanLists * kListLen;
@@ -435,9 +444,11 @@ int launch_dense_scan_group(anrag_index *idx, hipStream_t st, const float *const
     const int d = idx->dim;
     const int grid = dense_scan_grid(idx);
     const uint32_t *allow = (idx->d_dense_src != nullptr) ? d_allow_bits : nullptr;
-    if (!d_scores_out && k >= 1 && k <= kListLen && idx->pf_on) {  // K1F / K1F8: shadow scan + exact rescoring (same lists)
+    if (!d_scores_out && prefilter_serves(idx, k)) {  // K1F / K1F8: shadow scan + exact rescoring (same lists)
+        // the bracket is on this stream: with finish_later it holds the shadow scan alone
         LaunchTimer t(idx, ANRAG_KERNEL_DENSE_SCAN, st, n_queries);
-        return launch_dense_prefilter_group(idx, st, d_queries, n_queries, k, allow, sets, dt);
+        if (int rc = launch_dense_prefilter_scan(idx, st, d_queries, n_queries, k, allow, sets)) return rc;
+        return finish_later ? ANRAG_OK : launch_dense_prefilter_finish(idx, st, d_queries, n_queries, k, sets, dt);
     }
     {
         LaunchTimer t(idx, ANRAG_KERNEL_DENSE_SCAN, st, n_queries);

@@ -75,7 +75,10 @@ typedef struct anrag_candidate {
 
 typedef struct anrag_index anrag_index;
 
-/* Kernel ids for anrag_profile_read */
+/* Kernel ids for anrag_profile_read.
+ * With the dense prefilter on, ANRAG_KERNEL_DENSE_SCAN brackets what the route launches on the scan's stream: in the
+ * three-stream hybrid pipeline the shadow scan ALONE (threshold and rescore run on the tail's stream, and a bracket
+ * cannot span streams); on the one-stream routes (the scan lanes) the shadow scan, the threshold and the rescore. */
 #define ANRAG_KERNEL_DENSE_SCAN 0    /* K1: N x D fp32 scan + per-wave top-k      */
 #define ANRAG_KERNEL_DENSE_BATCHED 1 /* K2: Q x N fp32 MFMA GEMM + top-k epilogue */
 #define ANRAG_KERNEL_BM25 2          /* K3: CSR postings scorer                   */
@@ -291,7 +294,9 @@ int anrag_hybrid_search(anrag_index *idx, const float *query, const int32_t *ter
  * secondary-stream order (anrag_index_sync waits for all streams).
  * Back-to-back queries pipeline: the scans stay adjacent on the primary stream;
  * BM25 and the tail of query i run under the scans of the following queries.
- * Three launches per query: K1, K3 and one tail kernel (list merges + WRRF).
+ * Three launches per query: K1, K3 and one tail kernel (list merges + WRRF).  With the
+ * dense prefilter, K1 is the shadow scan, and its threshold and rescore kernels run in
+ * front of the tail on the tail's stream, under the following scans as well.
  * At most 32 queries are in flight per index: the call blocks on the HOST (never
  * on the device) until the query 32 back has finished with its buffers.
  * A corpus of at most 1 GiB on the index's own streams takes another route: the query's three launches go back to back on
