@@ -1541,6 +1541,69 @@ int anrag_debug_alloc_calls(int64_t *out_calls) {
     return ANRAG_OK;
 }
 
+int anrag_debug_prefilter_read(anrag_index *idx, int32_t *out_form, int64_t *out_rows_per_wave, int32_t *out_batch_rows,
+                               void *out_image, float *out_meta) {
+    ANRAG_ENTER(idx);
+    int rc = sync_all(idx);
+    if (rc) return rc;
+    const int32_t form = idx->pf_on ? idx->pf_form : 0;
+    if (out_form) *out_form = form;
+    int64_t rpw = 0;
+    int32_t rw = 0;
+    if (form) dense_prefilter_geometry(idx, &rpw, &rw);
+    if (out_rows_per_wave) *out_rows_per_wave = rpw;
+    if (out_batch_rows) *out_batch_rows = rw;
+    ANRAG_REQUIRE(form != 0 || (!out_image && !out_meta), "the dense prefilter is off: nothing to read");
+    const size_t n = (size_t)idx->n_rows;
+    if (out_image)
+        ANRAG_HIP(hipMemcpy(out_image, idx->d_pf_img, n * idx->dim * (form == kPrefilterInt8 ? 1 : 2), hipMemcpyDeviceToHost));
+    if (out_meta)
+        ANRAG_HIP(hipMemcpy(out_meta, idx->d_pf_m, n * (form == kPrefilterInt8 ? 4 : 1) * sizeof(float),
+                            hipMemcpyDeviceToHost));
+    return ANRAG_OK;
+}
+
+int anrag_debug_prefilter_bounds(anrag_index *idx, const float *queries, int32_t n_queries, int32_t k,
+                                 const uint8_t *allow_source, int32_t n_sources, uint32_t sentinel, float *out_hi,
+                                 float *out_threshold) {
+    ANRAG_ENTER(idx);
+    ANRAG_REQUIRE(idx->d_emb != nullptr && idx->pf_on, "the dense prefilter is off");
+    ANRAG_REQUIRE(queries && out_hi && out_threshold, "NULL operand");
+    ANRAG_REQUIRE(n_queries >= 1 && n_queries <= kScanGroupMax, "a scan launch takes 1..%d queries", kScanGroupMax);
+    ANRAG_REQUIRE(k >= 1 && k <= ANRAG_FUSED_K_MAX, "1 <= k <= %d", ANRAG_FUSED_K_MAX);
+    ANRAG_REQUIRE(!(allow_source && !idx->d_dense_src), "a source filter needs source ids (anrag_dense_load)");
+    ANRAG_REQUIRE((sentinel & 0x7F800000u) == 0x7F800000u && (sentinel & 0x007FFFFFu) != 0 && sentinel != 0x7FC00000u,
+                  "the sentinel must be a NaN pattern other than the kernel's 0x7FC00000");
+    int rc = sync_all(idx);  // list sets 0 .. n_queries - 1 and the staging buffers are free behind this
+    if (rc) return rc;
+    hipStream_t st = idx->primary;
+    const uint32_t *d_allow = nullptr;
+    if ((rc = stage_allow(idx, st, allow_source, n_sources, idx->d_allow_a, reinterpret_cast<uint32_t *>(idx->h_pinned),
+                          &d_allow)))
+        return rc;
+    ANRAG_HIP(hipMemcpyAsync(idx->d_query, queries, (size_t)n_queries * idx->dim * sizeof(float), hipMemcpyHostToDevice, st));
+    int sets[kScanGroupMax];
+    const float *qs[kScanGroupMax];
+    for (int i = 0; i < n_queries; ++i) {
+        sets[i] = i;
+        qs[i] = idx->d_query + (int64_t)i * idx->dim;
+    }
+    ANRAG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(idx->d_pf_hi), (int)sentinel,
+                                (size_t)n_queries * idx->pf_hi_stride, st));
+    ANRAG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(idx->d_pf_thr), (int)sentinel, (size_t)n_queries, st));
+    const int64_t counted = idx->pf_queries;  // a diagnostic scan is not a query answered
+    rc = launch_dense_prefilter_scan(idx, st, qs, n_queries, k, d_allow, sets);
+    idx->pf_queries = counted;
+    if (rc) return rc;
+    if ((rc = launch_dense_prefilter_threshold(idx, st, qs, n_queries, k, sets))) return rc;
+    ANRAG_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < n_queries; ++i)
+        ANRAG_HIP(hipMemcpy(out_hi + (int64_t)i * idx->n_rows, idx->d_pf_hi + (int64_t)i * idx->pf_hi_stride,
+                            (size_t)idx->n_rows * sizeof(float), hipMemcpyDeviceToHost));
+    ANRAG_HIP(hipMemcpy(out_threshold, idx->d_pf_thr, (size_t)n_queries * sizeof(float), hipMemcpyDeviceToHost));
+    return ANRAG_OK;
+}
+
 int anrag_index_info(anrag_index *idx, int64_t *dense_rows, int32_t *dense_dim, int64_t *bm25_docs,
                      int64_t *bm25_postings, int64_t *hbm_bytes) {
     ANRAG_ENTER(idx);

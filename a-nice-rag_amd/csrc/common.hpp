@@ -319,6 +319,10 @@ int launch_dense_prefilter_scan(anrag_index *idx, hipStream_t stream, const floa
                                 int32_t k, const uint32_t *d_allow_bits, const int *sets);
 int launch_dense_prefilter_finish(anrag_index *idx, hipStream_t stream, const float *const *d_queries, int32_t n_queries,
                                   int32_t k, const int *sets, const DeferredTail &dt);
+// diagnostics (anrag_debug_prefilter_*): the finish half's threshold launch alone; the scan's rows per wave and batch
+int launch_dense_prefilter_threshold(anrag_index *idx, hipStream_t stream, const float *const *d_queries,
+                                     int32_t n_queries, int32_t k, const int *sets);
+void dense_prefilter_geometry(const anrag_index *idx, int64_t *rows_per_wave, int32_t *batch_rows);
 // `finish_later`: when the top-k goes through the prefilter, launch its scan half only; the caller then orders
 // launch_dense_scan_finish (same queries, k and sets; a no-op on every other route) behind it on a stream of its choice.
 int launch_dense_scan_group(anrag_index *idx, hipStream_t stream, const float *const *d_queries, int32_t n_queries,

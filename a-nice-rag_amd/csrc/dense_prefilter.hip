@@ -855,6 +855,19 @@ int launch_dense_prefilter_scan(anrag_index *idx, hipStream_t st, const float *c
     return ANRAG_OK;
 }
 
+// the threshold launch of the finish half, on its own for anrag_debug_prefilter_bounds
+static hipError_t launch_threshold(const PrefilterQueries &Q, hipStream_t st, int32_t n_queries, int grid, int32_t k) {
+    dense_prefilter_threshold_kernel<<<n_queries, kThrWaves * kWave, 0, st>>>(Q, grid * kScanWaves, k);
+    return hipGetLastError();
+}
+
+int launch_dense_prefilter_threshold(anrag_index *idx, hipStream_t st, const float *const *d_queries, int32_t n_queries,
+                                     int32_t k, const int *sets) {
+    const PrefilterQueries Q = prefilter_queries(idx, d_queries, n_queries, sets);
+    ANRAG_HIP(launch_threshold(Q, st, n_queries, dense_scan_grid(idx), k));
+    return ANRAG_OK;
+}
+
 int launch_dense_prefilter_finish(anrag_index *idx, hipStream_t st, const float *const *d_queries, int32_t n_queries,
                                   int32_t k, const int *sets, const DeferredTail &dt) {
     const PrefilterQueries Q = prefilter_queries(idx, d_queries, n_queries, sets);
@@ -862,14 +875,28 @@ int launch_dense_prefilter_finish(anrag_index *idx, hipStream_t st, const float 
     hipError_t err = hipSuccess;  // of the first launch that failed
     prefilter_dispatch(idx->dim, [&](auto ps) {
         using F = typename decltype(ps)::Full;
-        dense_prefilter_threshold_kernel<<<n_queries, kThrWaves * kWave, 0, st>>>(Q, grid * kScanWaves, k);
-        if ((err = hipGetLastError()) != hipSuccess) return;
+        if ((err = launch_threshold(Q, st, n_queries, grid, k)) != hipSuccess) return;
         dense_prefilter_rescore_kernel<F::kG, F::kCH><<<grid + (dt.out ? 1 : 0), kScanThreads, 0, st>>>(
             idx->d_emb, Q, idx->n_rows, idx->dim, k, idx->d_pf_survivors, dt);
         err = hipGetLastError();
     });
     ANRAG_HIP(err);
     return ANRAG_OK;
+}
+
+// The scan's row geometry for this index's form: a wave owns rows [w * rows_per_wave, (w + 1) * rows_per_wave) and
+// walks them in batches of batch_rows (RW of the scan kernel).  For tests that plant rows at the edges of a block.
+void dense_prefilter_geometry(const anrag_index *idx, int64_t *rows_per_wave, int32_t *batch_rows) {
+    *rows_per_wave = 0;
+    *batch_rows = 0;
+    prefilter_dispatch(idx->dim, [&](auto ps) {
+        using H = typename decltype(ps)::Half;
+        using Q4 = typename decltype(ps)::Quarter;
+        const int rw = idx->pf_form == kPrefilterInt8 ? kWave / Q4::kG * Q4::kR : kWave / H::kG * H::kR;
+        const int64_t total_waves = (int64_t)dense_scan_grid(idx) * kScanWaves;
+        *batch_rows = rw;
+        *rows_per_wave = ((idx->n_rows + total_waves - 1) / total_waves + rw - 1) / rw * rw;
+    });
 }
 
 }  // namespace anrag

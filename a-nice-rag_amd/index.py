@@ -219,6 +219,36 @@ class Index:
         nat.check(self._lib.anrag_dense_prefilter_stats(self.handle, C.byref(q), C.byref(s)))
         return q.value, s.value
 
+    def debug_prefilter_read(self, data: bool = True) -> dict:
+        """The prefilter as built (`anrag_debug_prefilter_read`): form (0 off, 1 fp16, 2 int8), rows_per_wave and
+        batch_rows of the scan and, with `data`, image ([n, d] float16 / int8) and meta ([n] / [n, 4] float32)."""
+        form, rpw, rw = C.c_int32(0), C.c_int64(0), C.c_int32(0)
+        nat.check(self._lib.anrag_debug_prefilter_read(self.handle, C.byref(form), C.byref(rpw), C.byref(rw), None, None))
+        out = {"form": form.value, "rows_per_wave": rpw.value, "batch_rows": rw.value}
+        if data and form.value:
+            int8 = form.value == 2
+            img = np.empty((self.n_rows, self.dim), np.int8 if int8 else np.float16)
+            meta = np.empty((self.n_rows, 4) if int8 else (self.n_rows,), np.float32)
+            nat.check(self._lib.anrag_debug_prefilter_read(self.handle, None, None, None, img.ctypes.data, meta.ctypes.data))
+            out["image"], out["meta"] = img, meta
+        return out
+
+    PREFILTER_SENTINEL = 0x7FA5A5A5  # a NaN whose bits differ from the scan's own 0x7FC00000
+
+    def debug_prefilter_bounds(self, queries, k: int, allow_source=None):
+        """One shadow scan + threshold launch for 1..16 queries (`anrag_debug_prefilter_bounds`)
+        -> (hi [nq, n_rows] float32, T [nq] float32); a row the scan did not write holds PREFILTER_SENTINEL's bits."""
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        assert q.shape[1] == self.dim, f"query dim {q.shape[1]} != index dim {self.dim}"
+        allow, ns = _allow_bytes(allow_source)
+        hi = np.empty((q.shape[0], self.n_rows), np.float32)
+        thr = np.empty(q.shape[0], np.float32)
+        nat.check(self._lib.anrag_debug_prefilter_bounds(self.handle, q.ctypes.data, q.shape[0], int(k), nat.ptr(allow), ns,
+                                                         self.PREFILTER_SENTINEL, hi.ctypes.data, thr.ctypes.data))
+        return hi, thr
+
     def dense_scores(self, query) -> np.ndarray:
         q = _f32(query).reshape(-1)
         assert q.size == self.dim

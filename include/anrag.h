@@ -460,6 +460,22 @@ int anrag_index_info(anrag_index *idx, int64_t *dense_rows, int32_t *dense_dim,
 /* Device / pinned-host allocations and releases the library has made so far (process-wide; each one
  * synchronises the device).  A steady-state query loop must not move it: tests/test_gpu_no_alloc.py. */
 int anrag_debug_alloc_calls(int64_t *out_calls);
+/* The dense prefilter seen from outside, for tests of its score intervals (tests/test_gpu_dense_prefilter_bounds.py).
+ * Both wait for the index's streams; neither allocates.
+ * anrag_debug_prefilter_read: the form in use (0 off, 1 fp16, 2 int8), the scan's row geometry (a wave owns
+ * rows_per_wave consecutive rows and walks them batch_rows at a time) and, each nullable, the image as built
+ * (host, n_rows x dim fp16 values / int8 codes) and the per-row data (host, fp16: n_rows radii m; int8: n_rows x
+ * {s_e, m1, m2, 0}). */
+int anrag_debug_prefilter_read(anrag_index *idx, int32_t *out_form, int64_t *out_rows_per_wave, int32_t *out_batch_rows,
+                               void *out_image, float *out_meta);
+/* One shadow-scan launch and one threshold launch, as a group of 1..16 queries of the product runs them (list sets
+ * 0 .. n_queries - 1, the primary stream), without the rescore.  The sets' hi rows and thresholds are first filled with
+ * `sentinel` (the bits of a NaN other than 0x7FC00000, the NaN the scan stores for rows the filter rejects), so that a
+ * row the scan did not write shows.  queries host [n_queries][dim]; allow_source as for anrag_dense_search;
+ * out_hi host [n_queries][n_rows]: the upper bound of each row's fp32 score; out_threshold host [n_queries]: T. */
+int anrag_debug_prefilter_bounds(anrag_index *idx, const float *queries, int32_t n_queries, int32_t k,
+                                 const uint8_t *allow_source, int32_t n_sources, uint32_t sentinel, float *out_hi,
+                                 float *out_threshold);
 
 #ifdef __cplusplus
 }

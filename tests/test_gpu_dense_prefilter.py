@@ -3,6 +3,8 @@ answers -- the same ids and the same fp32 score bits -- on ordinary and adversar
 import numpy as np
 import pytest
 
+import prefilter_model as pm
+
 pytestmark = pytest.mark.gpu
 
 
@@ -44,7 +46,8 @@ def _same(off, on):
             assert np.array_equal(a, b)
 
 
-@pytest.mark.parametrize("d,n", [(256, 300_000), (512, 50_000), (768, 60_000), (1024, 50_000)])
+@pytest.mark.parametrize("d,n", [(256, 300_000), (512, 50_000), (768, 60_000), (1024, 50_000), (1536, 20_000),
+                                 (2048, 20_000)])
 def test_on_off_bit_identical(Index, d, n):
     e, rng = _corpus(n, d, seed=d)
     src = (np.arange(n) % 300).astype(np.uint16)
@@ -53,7 +56,7 @@ def test_on_off_bit_identical(Index, d, n):
     with Index(0) as idx:
         idx.dense_load(e, source_id=src)
         for k in (1, 10, 25, 64):
-            for nq in (1, 3, 8, 15):  # 15: groups of 8 + 7 (anrag_dense_search's launches)
+            for nq in (1, 3, 8, 15, 16):  # 15: groups of 8 + 7 (anrag_dense_search's launches)
                 q = _planted(e, rng, nq)
                 _same(*_both(idx, lambda: idx.dense_search(q, k)))
                 _same(*_both(idx, lambda: idx.dense_search(q, k, allow_source=allow)))
@@ -126,9 +129,14 @@ def test_adversarial_rows(Index):
     e[303, 7] = np.nan                             # a NaN row (ranks first, as +inf)
     e[304, 3] = np.inf
     e[305, 9] = -np.inf
+    # rows whose fp32 score sits at an end of the interval (prefilter_model.py), k + 3 of them with fp16 values of their
+    # own and the highest scores of the corpus: the k-th place falls among them, so losing one changes the answer
+    q_sat = pm.sat_fp16_row(d, np.random.default_rng(d))[0]
+    for i in range(k + 3):
+        e[400 + i] = pm.sat_fp16_row(d, rng, side=1 if i % 2 else -1, aligned=True, sign=np.sign(q_sat))[1]
     with Index(0) as idx:
         idx.dense_load(e)
-        for qq in (q, -q, np.zeros(d, np.float32), np.full(d, np.nan, np.float32), q * 1e30):
+        for qq in (q, -q, np.zeros(d, np.float32), np.full(d, np.nan, np.float32), q * 1e30, q_sat, -q_sat):
             for kk in (1, k, 64):
                 _same(*_both(idx, lambda: idx.dense_search(qq, kk)))
         allow = np.zeros(2, np.uint8)

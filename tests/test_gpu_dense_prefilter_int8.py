@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import prefilter_model as pm
 from test_build_resources import CSRC, LLVM, _kernels
 
 gpu = pytest.mark.gpu
@@ -145,9 +146,18 @@ def test_int8_adversarial_rows(Index):
     e[308, 5] = 30.0
     e[309:320] = 0.0                               # all-zero rows
     e[320] = e[kth] * 1e25                         # past the 2^60 cap of the radius
+    # rows whose fp32 score sits at an end of the interval (prefilter_model.py), k + 3 of them with codes of their own
+    # and the highest scores of the corpus: the k-th place falls among them, so losing one changes the answer; and the
+    # pair of rows that saturates the query term of the radius
+    q_sat = pm.sat_i8_row(d, np.random.default_rng(d))[0]
+    for i in range(k + 3):
+        e[400 + i] = pm.sat_i8_row(d, rng, side=1 if i % 2 else -1, aligned=True, sign=np.sign(q_sat))[1]
+    q_qt, e_qt = pm.sat_i8_query(d, np.random.default_rng(d + 1))
+    e[440], e[441] = e_qt, -e_qt
     with Index(0) as idx:
         idx.dense_load(e)
-        for qq in (q, -q, np.zeros(d, np.float32), np.full(d, np.nan, np.float32), q * 1e30, q * 1e-30):
+        for qq in (q, -q, np.zeros(d, np.float32), np.full(d, np.nan, np.float32), q * 1e30, q * 1e-30, q_sat, -q_sat,
+                   q_qt, -q_qt):
             for kk in (1, k, 64):
                 _same(*_both(idx, lambda: idx.dense_search(qq, kk)))
         spiky = q.copy()
