@@ -19,7 +19,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ANRAG_LIB") or os.path.join(_HERE, "libanrag.so")
 
 OK = 0
+ERR_UNSUPPORTED = -6  # the route exists for one index, not for a shard group: fatal, never "log and return empty"
 FUSED_K_MAX = 64
+GROUP_MAX_SHARDS = 16
 KERNEL_DENSE_SCAN, KERNEL_DENSE_BATCHED, KERNEL_BM25, KERNEL_SELECT, KERNEL_WRRF = range(5)
 
 
@@ -98,6 +100,21 @@ _SIGNATURES = {
     "anrag_debug_prefilter_bounds": [_p, _p, _i32, _i32, _p, _i32, C.c_uint32, _p, _p],
     "anrag_rank_batch": [_p, _i32, _i32, _i32, _f64, _i32, _i64, _p, _p, _p, _p, _p],
     "anrag_rank_caps": [C.POINTER(_i32), C.POINTER(_i32)],
+    "anrag_shard_group_create": [_p, _i32, C.POINTER(_p)],
+    "anrag_shard_group_destroy": [_p],
+    "anrag_shard_group_dense_load": [_p, _p, _i64, _i32, _p, _p, _i64],
+    "anrag_shard_group_bm25_load": [_p, _p, _i64, _p, _p, _p, _p, _i64, _f64, _f64, _f64, _p, _p, _i64],
+    "anrag_shard_group_hybrid_search": [_p, _p, _p, _i32, _i32, _f64, _f64, _f64, _i32, _p, _i32, _p, _i32, _p, _p, _p],
+    "anrag_shard_group_hybrid_search_batch": [_p, _p, _p, _p, _i32, _i32, _f64, _f64, _f64, _i32, _p, _i32, _p, _i32, _p,
+                                              _p, _p],
+    "anrag_shard_group_dense_search": [_p, _p, _i32, _i32, _p, _i32, _p, _p, _p],
+    "anrag_shard_group_dense_search_f64": [_p, _p, _i32, _p, _i32, _p, _p, _p],
+    "anrag_shard_group_bm25_search": [_p, _p, _i32, _i32, _p, _i32, _p, _p, _p],
+    "anrag_shard_group_debug_enqueue": [_p, C.POINTER(_i64), C.POINTER(_i64)],
+    "anrag_shard_group_set_dense_prefilter": [_p, _i32],
+    "anrag_shard_group_sync": [_p],
+    "anrag_shard_group_info": [_p, C.POINTER(_i32), _p, _p, C.POINTER(_i64)],
+    "anrag_shard_group_shard": [_p, _i32, C.POINTER(_p)],
 }
 EXPORTS = tuple(_SIGNATURES) + ("anrag_last_error",)
 

@@ -1616,3 +1616,32 @@ int anrag_index_info(anrag_index *idx, int64_t *dense_rows, int32_t *dense_dim, 
 }
 
 }  // extern "C"
+
+namespace anrag {
+
+// What a shard group (shard_group.hip) asks of one of its shards: the body of anrag_hybrid_candidates_group_device
+// for up to kScanGroupMax queries, without that entry's demand for both legs -- a NULL query vector is no dense leg,
+// n_terms == 0 beside a dense leg no BM25 leg (its half of the 2k block is padding).  Always the three-stream
+// pipeline: the blocks are complete in fusion-stream order.
+int enqueue_candidates_2k(anrag_index *idx, const CandQuery *q, int32_t n, int32_t k, const uint32_t *d_allow_dense,
+                          const uint32_t *d_allow_bm25) {
+    ANRAG_ENTER(idx);
+    ANRAG_REQUIRE(q && n >= 1 && n <= kScanGroup, "candidate group of %d queries", n);
+    GroupQuery g[kScanGroup];
+    for (int i = 0; i < n; ++i) g[i] = GroupQuery{q[i].d_query, q[i].d_terms, q[i].n_terms, q[i].d_out, nullptr};
+    return hybrid_enqueue_group(idx, kTailCandidates2k, g, n, k, 1.0, 1.0, 0.0, 0, d_allow_dense, d_allow_bm25);
+}
+
+// The shard's grow-only call pool, for the operands a group call stages on it (nothing of the shard's is in flight:
+// every group call ends with a host wait).
+int reserve_call_pool(anrag_index *idx, int64_t bytes, char **out) {
+    ANRAG_ENTER(idx);
+    if (idx->call_pool.bytes < bytes) {  // growing replaces the block
+        if (int rc = settle_pipeline(idx)) return rc;
+        if (int rc = ensure_pool(idx, idx->call_pool, bytes)) return rc;
+    }
+    *out = idx->call_pool.p;
+    return ANRAG_OK;
+}
+
+}  // namespace anrag

@@ -390,5 +390,16 @@ int launch_merge_fuse(anrag_index *idx, hipStream_t st, const anrag_candidate *d
                       int32_t n_queries, anrag_candidate *d_out, int32_t *d_count);
 int launch_merge_candidates(anrag_index *idx, hipStream_t stream, const anrag_candidate *d_lists,
                             int32_t n_lists, int32_t k, int64_t list_stride, anrag_candidate *d_out);
+// One shard's share of a shard group's exchange group (api.hip; shard_group.hip calls them): 2k candidate records per
+// query into d_out, complete in the shard's fusion-stream order; and the shard's call pool for staged operands.
+struct CandQuery {
+    const float *d_query;   // NULL: no dense leg
+    const int32_t *d_terms;
+    int32_t n_terms;        // 0 beside a dense leg: no BM25 leg
+    anrag_candidate *d_out;
+};
+int enqueue_candidates_2k(anrag_index *idx, const CandQuery *q, int32_t n, int32_t k, const uint32_t *d_allow_dense,
+                          const uint32_t *d_allow_bm25);
+int reserve_call_pool(anrag_index *idx, int64_t bytes, char **out);
 
 }  // namespace anrag

@@ -24,13 +24,22 @@ import numpy as np
 import pandas as pd
 
 from .bm25_index import Bm25Index
-from .index import Index
+from .index import Index, ShardGroup, parse_devices
 
 ATTR = "_anrag"
 
 
 def _default_device() -> int:
     return int(os.environ.get("ANRAG_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+
+
+def _open_index(device: Optional[int] = None):
+    """The index a handle holds.  `ANRAG_DEVICES=0,1,...` (repeats allowed), read where the default device is read: a
+    `ShardGroup` over those devices -- one corpus, several GPUs, this process -- instead of one `Index`.  A group that
+    cannot be built raises; nothing falls back to one index."""
+    if device is None and os.environ.get("ANRAG_DEVICES") is not None:
+        return ShardGroup(parse_devices(os.environ["ANRAG_DEVICES"]))
+    return Index(_default_device() if device is None else device)
 
 
 def intern_sources(sources: Sequence[Optional[str]]) -> Tuple[np.ndarray, List[Optional[str]]]:
@@ -52,7 +61,7 @@ class DenseHandle:
     """A DataFrame's corpus matrix resident in HBM (rows == DataFrame positions)."""
 
     def __init__(self, embeddings: np.ndarray, sources: Sequence[Optional[str]], device: Optional[int] = None):
-        self.index = Index(_default_device() if device is None else device)
+        self.index = _open_index(device)
         self.source_id, self.distinct_sources = intern_sources(sources)
         self.index.dense_load(embeddings, source_id=self.source_id)
         self.n_rows, self.dim = embeddings.shape
@@ -92,7 +101,7 @@ class Bm25Proxy:
         self.doc_len = stats.doc_len
         self.average_idf = stats.average_idf
         self.source_id, self.distinct_sources = intern_sources(section_sources)
-        self.index = Index(_default_device() if device is None else device)
+        self.index = _open_index(device)
         self.index.bm25_load(stats.indptr, stats.post_doc, stats.post_tf, stats.idf, stats.doc_len, stats.avgdl,
                              stats.k1, stats.b, source_id=self.source_id)
         self.fused: Dict[int, "FusedPair"] = {}
@@ -105,6 +114,8 @@ class Bm25Proxy:
         return self.stats.term_ids(tokens)
 
     def get_scores(self, query: Sequence[str]) -> np.ndarray:
+        """On a shard group (`ANRAG_DEVICES`) this raises `AnragError` (ANRAG_ERR_UNSUPPORTED): a group serves ranked
+        lists, not score dumps."""
         return self.index.bm25_scores(self.term_ids(query))
 
     @classmethod

@@ -97,6 +97,227 @@ def rank_batch(legs: Sequence[dict], n_queries: int, similarity_k: int, wrrf_k: 
     return out_id, out_score, count
 
 
+def parse_devices(text: str) -> list:
+    """`ANRAG_DEVICES`: "0, 1,1" -> [0, 1, 1] (repeats allowed: several shards on one GPU).  Empty, negative,
+    non-numeric entries and more than 16 of them are errors."""
+    parts = [p.strip() for p in str(text).split(",")]
+    if not parts or any(p == "" for p in parts):
+        raise ValueError(f"ANRAG_DEVICES={text!r}: expected a comma-separated list of device numbers")
+    if not all(p.isdigit() for p in parts):
+        raise ValueError(f"ANRAG_DEVICES={text!r}: device numbers must be non-negative integers")
+    if len(parts) > nat.GROUP_MAX_SHARDS:
+        raise ValueError(f"ANRAG_DEVICES={text!r}: at most {nat.GROUP_MAX_SHARDS} shards")
+    return [int(p) for p in parts]
+
+
+def group_bounds(n: int, n_shards: int) -> list:
+    """Block bounds [lo_0, ..., lo_S] a shard group cuts `n` rows into (the rule of `sharded.shard_bounds`)."""
+    base, extra = divmod(int(n), int(n_shards))
+    return [i * base + min(i, extra) for i in range(n_shards + 1)]
+
+
+class ShardGroup:
+    """Owns an `anrag_shard_group*`: ONE corpus over several GPUs (or several shards of one GPU) in one process, with
+    `Index`'s method names and return shapes for what a group serves -- every answer equals the single index's, ids,
+    counts and score bits.  `dense_scores`, `bm25_scores` and the ranking route (`rank_batch` takes `Index` legs: a
+    group has no `handle`) raise `AnragError` with code `ERR_UNSUPPORTED`."""
+
+    def __init__(self, devices: Sequence[int]):
+        self._lib = nat.load_library()
+        self.devices = [int(d) for d in devices]
+        dev = np.ascontiguousarray(self.devices, dtype=np.int32)
+        h = C.c_void_p()
+        nat.check(self._lib.anrag_shard_group_create(dev.ctypes.data if dev.size else None, int(dev.size), C.byref(h)))
+        self._g = h
+        self.device = self.devices[0]
+        self.n_shards = len(self.devices)
+        self.n_rows = 0
+        self.dim = 0
+        self.n_docs = 0
+
+    def close(self) -> None:
+        if getattr(self, "_g", None):
+            self._lib.anrag_shard_group_destroy(self._g)
+            self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def group(self) -> C.c_void_p:
+        if not self._g:
+            raise nat.AnragError(-3, "shard group is closed")
+        return self._g
+
+    @property
+    def handle(self):
+        raise nat.AnragError(nat.ERR_UNSUPPORTED, "a shard group has no anrag_index handle: the ranking route "
+                                                  "(anrag_rank_batch) and the *_device entries take one index")
+
+    def shard(self, i: int) -> C.c_void_p:
+        """Borrowed `anrag_index*` of shard i (stats, profiling, tests); it dies with the group."""
+        h = C.c_void_p()
+        nat.check(self._lib.anrag_shard_group_shard(self.group, int(i), C.byref(h)))
+        return h
+
+    def shard_prefilter_stats(self, i: int) -> tuple:
+        q, s = C.c_int64(0), C.c_int64(0)
+        nat.check(self._lib.anrag_dense_prefilter_stats(self.shard(i), C.byref(q), C.byref(s)))
+        return q.value, s.value
+
+    def sync(self) -> None:
+        nat.check(self._lib.anrag_shard_group_sync(self.group))
+
+    def set_dense_prefilter(self, mode: int = -1) -> None:
+        nat.check(self._lib.anrag_shard_group_set_dense_prefilter(self.group, int(mode)))
+
+    def dense_load(self, embeddings, source_id=None, doc_id=None, doc_id_base: int = 0) -> None:
+        """Host operands only (a numpy matrix): the group cuts it into row blocks, one per shard."""
+        if isinstance(embeddings, tuple):
+            raise nat.AnragError(nat.ERR_UNSUPPORTED, "a shard group loads host arrays, not device buffers")
+        keep = _f32(embeddings)
+        assert keep.ndim == 2
+        n, d = keep.shape
+        src = None if source_id is None else np.ascontiguousarray(source_id, dtype=np.uint16)
+        doc = None if doc_id is None else np.ascontiguousarray(doc_id, dtype=np.int64)
+        assert src is None or src.shape == (n,)
+        assert doc is None or doc.shape == (n,)
+        nat.check(self._lib.anrag_shard_group_dense_load(self.group, keep.ctypes.data, n, d, nat.ptr(src), nat.ptr(doc),
+                                                         int(doc_id_base)))
+        self.n_rows, self.dim = int(n), int(d)
+
+    def bm25_load(self, indptr, post_doc, post_tf, idf, doc_len, avgdl: float, k1: float, b: float,
+                  source_id=None, doc_id=None, doc_id_base: int = 0) -> None:
+        if isinstance(post_doc, tuple) or isinstance(post_tf, tuple):
+            raise nat.AnragError(nat.ERR_UNSUPPORTED, "a shard group loads host arrays, not device buffers")
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        idf = np.ascontiguousarray(idf, dtype=np.float64)
+        doc_len = np.ascontiguousarray(doc_len, dtype=np.int32)
+        post_doc = np.ascontiguousarray(post_doc, dtype=np.int32)
+        post_tf = np.ascontiguousarray(post_tf, dtype=np.int32)
+        n_terms, n_docs = indptr.size - 1, doc_len.size
+        assert idf.size == n_terms and post_doc.size == post_tf.size == int(indptr[-1])
+        src = None if source_id is None else np.ascontiguousarray(source_id, dtype=np.uint16)
+        doc = None if doc_id is None else np.ascontiguousarray(doc_id, dtype=np.int64)
+        nat.check(self._lib.anrag_shard_group_bm25_load(self.group, indptr.ctypes.data, n_terms, post_doc.ctypes.data,
+                                                        post_tf.ctypes.data, idf.ctypes.data, doc_len.ctypes.data, n_docs,
+                                                        float(avgdl), float(k1), float(b), nat.ptr(src), nat.ptr(doc),
+                                                        int(doc_id_base)))
+        self.n_docs = int(n_docs)
+
+    def dense_search(self, queries, k: int, allow_source=None):
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        if self.n_rows == 0:
+            raise nat.AnragError(-3, "dense search before dense_load")
+        assert q.shape[1] == self.dim, f"query dim {q.shape[1]} != index dim {self.dim}"
+        nq = q.shape[0]
+        allow, ns = _allow_bytes(allow_source)
+        doc = np.empty((nq, k), np.int64)
+        score = np.empty((nq, k), np.float32)
+        count = np.empty(nq, np.int32)
+        nat.check(self._lib.anrag_shard_group_dense_search(self.group, q.ctypes.data, nq, int(k), nat.ptr(allow), ns,
+                                                           doc.ctypes.data, score.ctypes.data, count.ctypes.data))
+        return doc, score, count
+
+    def dense_search_f64(self, query, k: int, allow_source=None):
+        q = np.ascontiguousarray(query, dtype=np.float64).reshape(-1)
+        assert q.size == self.dim, f"query dim {q.size} != index dim {self.dim}"
+        allow, ns = _allow_bytes(allow_source)
+        doc = np.empty(k, np.int64)
+        score = np.empty(k, np.float64)
+        count = np.zeros(1, np.int32)
+        nat.check(self._lib.anrag_shard_group_dense_search_f64(self.group, q.ctypes.data, int(k), nat.ptr(allow), ns,
+                                                               doc.ctypes.data, score.ctypes.data, count.ctypes.data))
+        return doc, score, int(count[0])
+
+    def bm25_search(self, term_ids: Sequence[int], k: int, allow_source=None):
+        t = np.ascontiguousarray(term_ids, dtype=np.int32)
+        allow, ns = _allow_bytes(allow_source)
+        doc = np.empty(k, np.int64)
+        score = np.empty(k, np.float64)
+        count = np.zeros(1, np.int32)
+        nat.check(self._lib.anrag_shard_group_bm25_search(self.group, nat.ptr(t) if t.size else None, int(t.size), int(k),
+                                                          nat.ptr(allow), ns, doc.ctypes.data, score.ctypes.data,
+                                                          count.ctypes.data))
+        return doc, score, int(count[0])
+
+    def dense_scores(self, query) -> np.ndarray:
+        """Not served by a group: raises `AnragError` (`ERR_UNSUPPORTED`)."""
+        raise nat.AnragError(nat.ERR_UNSUPPORTED, "a shard group does not serve score dumps (anrag_dense_scores): use one index")
+
+    def bm25_scores(self, term_ids: Sequence[int]) -> np.ndarray:
+        """Not served by a group: raises `AnragError` (`ERR_UNSUPPORTED`)."""
+        raise nat.AnragError(nat.ERR_UNSUPPORTED,
+                             "a shard group does not serve score dumps (anrag_bm25_scores / get_scores): use one index")
+
+    def enqueue_stats(self) -> tuple:
+        """(exchange groups enqueued so far, host nanoseconds spent enqueuing them)."""
+        n, ns = C.c_int64(0), C.c_int64(0)
+        nat.check(self._lib.anrag_shard_group_debug_enqueue(self.group, C.byref(n), C.byref(ns)))
+        return n.value, ns.value
+
+    def hybrid_search(self, query, term_ids: Sequence[int], similarity_k: int, w_dense: float, w_bm25: float,
+                      wrrf_k: float, top_n: int, allow_dense=None, allow_bm25=None):
+        q = _f32(query).reshape(-1)
+        assert q.size == self.dim
+        t = np.ascontiguousarray(term_ids, dtype=np.int32)
+        ad, nd = _allow_bytes(allow_dense)
+        ab, nb = _allow_bytes(allow_bm25)
+        out_id = np.empty(top_n, np.int64)
+        out_score = np.empty(top_n, np.float64)
+        count = np.zeros(1, np.int32)
+        nat.check(self._lib.anrag_shard_group_hybrid_search(
+            self.group, q.ctypes.data, nat.ptr(t) if t.size else None, int(t.size), int(similarity_k), float(w_dense),
+            float(w_bm25), float(wrrf_k), int(top_n), nat.ptr(ad), nd, nat.ptr(ab), nb, out_id.ctypes.data,
+            out_score.ctypes.data, count.ctypes.data))
+        m = int(count[0])
+        return out_id[:m], out_score[:m]
+
+    def hybrid_search_batch(self, queries, term_lists: Sequence[Sequence[int]], similarity_k: int, w_dense: float,
+                            w_bm25: float, wrrf_k: float, top_n: int, allow_dense=None, allow_bm25=None):
+        """The pipelined batch = 1 kernels on every shard; row i equals `hybrid_search(queries[i], term_lists[i], ...)`."""
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        nq = q.shape[0]
+        assert q.shape[1] == self.dim and len(term_lists) == nq
+        offsets = np.zeros(nq + 1, dtype=np.int64)
+        np.cumsum([len(t) for t in term_lists], out=offsets[1:])
+        terms = (np.concatenate([np.asarray(t, dtype=np.int32).reshape(-1) for t in term_lists]).astype(np.int32)
+                 if offsets[-1] else np.zeros(0, np.int32))
+        terms = np.ascontiguousarray(terms)
+        ad, nd = _allow_bytes(allow_dense)
+        ab, nb = _allow_bytes(allow_bm25)
+        out_id = np.empty((nq, top_n), np.int64)
+        out_score = np.empty((nq, top_n), np.float64)
+        count = np.zeros(nq, np.int32)
+        nat.check(self._lib.anrag_shard_group_hybrid_search_batch(
+            self.group, q.ctypes.data, nat.ptr(terms) if terms.size else None, offsets.ctypes.data, nq,
+            int(similarity_k), float(w_dense), float(w_bm25), float(wrrf_k), int(top_n), nat.ptr(ad), nd, nat.ptr(ab), nb,
+            out_id.ctypes.data, out_score.ctypes.data, count.ctypes.data))
+        return out_id, out_score, count
+
+    def info(self) -> dict:
+        n, h = C.c_int32(), C.c_int64()
+        rows = np.zeros(nat.GROUP_MAX_SHARDS + 1, np.int64)
+        docs = np.zeros(nat.GROUP_MAX_SHARDS + 1, np.int64)
+        nat.check(self._lib.anrag_shard_group_info(self.group, C.byref(n), rows.ctypes.data, docs.ctypes.data, C.byref(h)))
+        s = n.value
+        return dict(n_shards=s, dense_row_lo=rows[: s + 1].tolist(), bm25_doc_lo=docs[: s + 1].tolist(),
+                    dense_rows=int(rows[s]), dense_dim=self.dim, bm25_docs=int(docs[s]), hbm_bytes=h.value)
+
+
 class Index:
     """Owns an `anrag_index*`.  Not copyable; `close()` (or GC) frees the HBM."""
 

@@ -51,7 +51,7 @@ class RetrievalEvaluationSystem:
             except Exception as e:
                 from ._native import AnragError
 
-                if isinstance(e, AnragError) and e.code in (-100, -5):
+                if isinstance(e, AnragError) and e.code in (-100, -5, -6):
                     raise  # no library / no GPU is not a data problem
                 logger.error(f"Failed to load {source.value}: {e}")
                 self.embeddings_data[source] = {}
@@ -192,7 +192,7 @@ class RetrievalEvaluationSystem:
         except Exception as e:
             from ._native import AnragError
 
-            if isinstance(e, AnragError) and e.code in (-100, -5):
+            if isinstance(e, AnragError) and e.code in (-100, -5, -6):
                 raise
             logger.error(f"Error in retrieval processing: {e}")
             return []
@@ -251,6 +251,19 @@ class RetrievalEvaluationSystem:
         return [names[g] for g in gids.tolist()]
 
     # ------------------------------------------------------------------ query lists
+    @staticmethod
+    def _on_shard_group(embeddings_dict, bm25) -> bool:
+        """True when a frame of this info source, or its BM25 proxy, lives on a `ShardGroup`: lists of queries then go
+        through `hybrid_search_batch` (the pipelined batch = 1 kernels) or query by query (large k: the cold routes)."""
+        from .database_manager import ATTR
+        from .index import ShardGroup
+
+        for df in embeddings_dict.values():
+            h = getattr(df, "attrs", {}).get(ATTR) if df is not None else None
+            if h is not None and isinstance(h.index, ShardGroup):
+                return True
+        return isinstance(getattr(bm25, "index", None), ShardGroup)
+
     def _rank_batch(self, queries: List[Dict], params: Dict, expected: Optional[List[str]] = None):
         """The ids-only route for a LIST of queries as ONE `anrag_rank_batch` (rank_batch.hip): every active dense model
         and BM25 scored into tiles, ranked and fused on the device -- what `retrieval_eval.py`'s k = 12,000 configurations
@@ -282,6 +295,8 @@ class RetrievalEvaluationSystem:
         bm25_tuple = self.bm25_data.get(source_enum)
         bm25, bm25_sections, bm25_section_ids = bm25_tuple if bm25_tuple else (None, [], [])
         want_bm25 = bool(params.get("use_hybrid_search", False)) and bm25 is not None and model_weights.get("BM25", 0) > 0
+        if self._on_shard_group(embeddings_dict, bm25):
+            return None  # a shard group (ANRAG_DEVICES) does not serve anrag_rank_batch: skipped up front, not tried and caught
         if params.get("use_reranker", True) and any(q.get("query_text") for q in queries):
             return None  # reranking materialises documents: per query
         from .database_manager import DenseHandle
@@ -366,7 +381,7 @@ class RetrievalEvaluationSystem:
             except Exception as e:
                 from ._native import AnragError
 
-                if isinstance(e, AnragError) and e.code in (-100, -5):
+                if isinstance(e, AnragError) and e.code in (-100, -5, -6):
                     raise
                 logger.info(f"Batched ranking not applicable, answering one by one: {e}")
                 rows = None
@@ -403,7 +418,7 @@ class RetrievalEvaluationSystem:
             except Exception as e:
                 from ._native import AnragError
 
-                if isinstance(e, AnragError) and e.code in (-100, -5):
+                if isinstance(e, AnragError) and e.code in (-100, -5, -6):
                     raise
                 rows = None
             if rows is not None:
@@ -441,7 +456,7 @@ class RetrievalEvaluationSystem:
         except Exception as e:
             from ._native import AnragError
 
-            if isinstance(e, AnragError) and e.code in (-100, -5):
+            if isinstance(e, AnragError) and e.code in (-100, -5, -6):
                 raise
             logger.error(f"Batched retrieval failed, answering one by one: {e}")
             out = None
@@ -458,7 +473,7 @@ class RetrievalEvaluationSystem:
         except Exception as e:
             from ._native import AnragError
 
-            if isinstance(e, AnragError) and e.code in (-100, -5):
+            if isinstance(e, AnragError) and e.code in (-100, -5, -6):
                 raise
             logger.info(f"Batched ranking not applicable: {e}")
             return None

@@ -25,7 +25,8 @@ from .database_manager import ATTR, Bm25Proxy, DenseHandle, FusedPair
 from .index import Index
 from .preprocess_bm25 import preprocess_text
 
-_FATAL = (-100, -5)  # library not built / no gfx950 device: never "log and return empty"
+_FATAL = (-100, -5, -6)  # library not built / no gfx950 device / a route a shard group does not serve: never "log and
+                         # return empty" (an evaluation run must not report all-miss metrics for a route that was not there)
 
 
 def _prefixes(filename_type_filter: str) -> Tuple[str, ...]:

@@ -37,8 +37,10 @@
  *   - ordering rule everywhere: score descending, then ROW ascending (rows are
  *     what the reference's tie behaviour is stated in: its filtered BM25 path is
  *     a stable sort = low row first, :233; its numpy paths leave ties
- *     unspecified).  Across shards the tie-break is doc id ascending, which is
- *     the same thing under row sharding with doc id = doc_id_base + row.
+ *     unspecified).  Across the ranks of the torch.distributed path the tie-break
+ *     is doc id ascending, which is the same thing under row sharding with
+ *     doc id = doc_id_base + row; a shard group (below) merges in shard order,
+ *     which is (score desc, global row asc) for any doc id map.
  */
 #ifndef ANRAG_H
 #define ANRAG_H
@@ -57,6 +59,7 @@ extern "C" {
 #define ANRAG_ERR_STATE (-3)   /* e.g. search before load                        */
 #define ANRAG_ERR_NOMEM (-4)   /* host or device allocation failed               */
 #define ANRAG_ERR_NODEVICE (-5) /* no usable gfx950 device                       */
+#define ANRAG_ERR_UNSUPPORTED (-6) /* the route exists for one index, not for a shard group */
 
 /* Largest k served by the fused in-register per-wave top-k (one candidate per
  * lane of a 64-wide wavefront).  Larger k (retrieval_eval.py:142-143 uses 12000)
@@ -476,6 +479,75 @@ int anrag_debug_prefilter_read(anrag_index *idx, int32_t *out_form, int64_t *out
 int anrag_debug_prefilter_bounds(anrag_index *idx, const float *queries, int32_t n_queries, int32_t k,
                                  const uint8_t *allow_source, int32_t n_sources, uint32_t sentinel, float *out_hi,
                                  float *out_threshold);
+
+/* ------------------------------------------------------------------ shard group
+ * ONE corpus over several anrag_index objects in ONE process (the reference is one process: one RAGSystem for all
+ * Streamlit threads, src/app.py:17-27): n_shards (1..ANRAG_GROUP_MAX_SHARDS) indexes, shard i on devices[i].  The same
+ * device may appear several times ({0,0,0,0} = four shards on one GPU): a supported configuration.  Dense rows and BM25
+ * documents are cut, independently, into contiguous blocks that differ by at most one row (shard i of n rows:
+ * [i*(n/S) + min(i, n%S), ...)); every shard gets the GLOBAL idf / avgdl / k1 / b, so a score has the bits the single
+ * index gives it.  The search entries take the arguments of their anrag_* namesakes, return what those return for ONE
+ * index loaded with the same operands -- ids, counts and score bits -- and wait for their result.
+ *
+ * Hot route (hybrid, dense and BM25 with k <= ANRAG_FUSED_K_MAX): per exchange group of up to 8 queries every shard
+ * enqueues its 2k candidate records per query (the three-stream pipeline of anrag_hybrid_candidates_group_device) into a
+ * slab of its own HBM and records an event on its fusion stream; shard 0's fusion stream waits for those events and
+ * runs ONE tail kernel for the group, which reads the other shards' slabs in place (peer access between distinct
+ * devices, enabled at create; staged with hipMemcpyPeerAsync where the devices cannot map each other), merges each
+ * modality's lists STABLY IN SHARD ORDER -- among equal scores the earlier shard, inside a shard the earlier position,
+ * stays ahead: (score desc, global row asc) -- and fuses as the single index's tail does.  No host sync and no
+ * collective between the shards; 4 exchange groups are in flight inside a batch call.  The steady state allocates
+ * nothing (anrag_debug_alloc_calls).
+ * Cold routes (k > ANRAG_FUSED_K_MAX, the fp64 query): the shards' host entry points one after the other and a stable
+ * merge of their lists on the host.  Serial and untuned on purpose.
+ * Not served: anrag_rank_batch and the K2 batched pass (a rank leg takes an anrag_index), the *_device entries, the
+ * score dumps: there is no group entry for them; a binding reports ANRAG_ERR_UNSUPPORTED (a-nice-rag_amd/index.py).
+ * A group is serialised by its own mutex for the whole call. */
+#define ANRAG_GROUP_MAX_SHARDS 16
+typedef struct anrag_shard_group anrag_shard_group;
+int anrag_shard_group_create(const int32_t *devices, int32_t n_shards, anrag_shard_group **out);
+int anrag_shard_group_destroy(anrag_shard_group *g);
+/* Host operands.  n_shards larger than n_rows / n_docs: ANRAG_ERR_INVALID. */
+int anrag_shard_group_dense_load(anrag_shard_group *g, const float *embeddings, int64_t n_rows, int32_t dim,
+                                 const uint16_t *source_id, const int64_t *doc_id, int64_t doc_id_base);
+int anrag_shard_group_bm25_load(anrag_shard_group *g, const int64_t *indptr, int64_t n_terms, const int32_t *post_doc,
+                                const int32_t *post_tf, const double *idf, const int32_t *doc_len, int64_t n_docs,
+                                double avgdl, double k1, double b, const uint16_t *source_id, const int64_t *doc_id,
+                                int64_t doc_id_base);
+int anrag_shard_group_hybrid_search(anrag_shard_group *g, const float *query, const int32_t *term_ids, int32_t n_terms,
+                                    int32_t similarity_k, double w_dense, double w_bm25, double wrrf_k, int32_t top_n,
+                                    const uint8_t *allow_dense, int32_t n_dense_sources, const uint8_t *allow_bm25,
+                                    int32_t n_bm25_sources, int64_t *out_id, double *out_score, int32_t *out_count);
+/* Always the pipelined batch = 1 kernels (the ranking route of anrag_hybrid_search_batch is not served). */
+int anrag_shard_group_hybrid_search_batch(anrag_shard_group *g, const float *queries, const int32_t *term_ids,
+                                          const int64_t *term_offsets, int32_t n_queries, int32_t similarity_k,
+                                          double w_dense, double w_bm25, double wrrf_k, int32_t top_n,
+                                          const uint8_t *allow_dense, int32_t n_dense_sources,
+                                          const uint8_t *allow_bm25, int32_t n_bm25_sources, int64_t *out_id,
+                                          double *out_score, int32_t *out_count);
+int anrag_shard_group_dense_search(anrag_shard_group *g, const float *queries, int32_t n_queries, int32_t k,
+                                   const uint8_t *allow_source, int32_t n_sources, int64_t *out_doc, float *out_score,
+                                   int32_t *out_count);
+int anrag_shard_group_dense_search_f64(anrag_shard_group *g, const double *query, int32_t k,
+                                       const uint8_t *allow_source, int32_t n_sources, int64_t *out_doc,
+                                       double *out_score, int32_t *out_count);
+int anrag_shard_group_bm25_search(anrag_shard_group *g, const int32_t *term_ids, int32_t n_terms, int32_t k,
+                                  const uint8_t *allow_source, int32_t n_sources, int64_t *out_doc, double *out_score,
+                                  int32_t *out_count);
+int anrag_shard_group_set_dense_prefilter(anrag_shard_group *g, int32_t mode); /* forwards to every shard */
+int anrag_shard_group_sync(anrag_shard_group *g);
+/* dense_row_lo / bm25_doc_lo (each nullable): n_shards + 1 block bounds (all 0 before the load); hbm_bytes: the shards'
+ * and the group's own. */
+int anrag_shard_group_info(anrag_shard_group *g, int32_t *n_shards, int64_t *dense_row_lo, int64_t *bm25_doc_lo,
+                           int64_t *hbm_bytes);
+/* Borrowed handle of shard i (stats, profiling, tests); it dies with the group.  Not to be used from another thread
+ * while a call on the group runs: the group enqueues on the shard's streams under its own mutex. */
+int anrag_shard_group_shard(anrag_shard_group *g, int32_t i, anrag_index **out);
+/* Exchange groups enqueued so far and the host time (ns) spent enqueuing them -- every shard's launches, the event
+ * records and waits, the tail launch; no uploads, no waiting for results --
+ * but including the shards' host-side back-pressure: in a GPU-bound run it reads the GPU's time per group, and the
+ * host's own cost only where the GPU never holds the host back.  scripts/measure_shard_group.py. */
+int anrag_shard_group_debug_enqueue(anrag_shard_group *g, int64_t *out_groups, int64_t *out_ns);
 
 #ifdef __cplusplus
 }
