@@ -47,6 +47,13 @@ class RankLeg(C.Structure):
                 ("doc_of_row", C.c_void_p), ("weight", C.c_double)]
 
 
+class GroupRankLeg(C.Structure):
+    """`anrag_group_rank_leg` (include/anrag.h): a leg of `anrag_shard_group_rank_batch`, a whole group or one index."""
+    _fields_ = [("group", C.c_void_p), ("idx", C.c_void_p), ("kind", C.c_int32), ("queries", C.c_void_p),
+                ("term_ids", C.c_void_p), ("term_offsets", C.c_void_p), ("allow_source", C.c_void_p),
+                ("n_sources", C.c_int32), ("doc_of_row", C.c_void_p), ("weight", C.c_double)]
+
+
 _lib: Optional[C.CDLL] = None
 
 _p = C.c_void_p
@@ -115,6 +122,7 @@ _SIGNATURES = {
     "anrag_shard_group_sync": [_p],
     "anrag_shard_group_info": [_p, C.POINTER(_i32), _p, _p, C.POINTER(_i64)],
     "anrag_shard_group_shard": [_p, _i32, C.POINTER(_p)],
+    "anrag_shard_group_rank_batch": [_p, _i32, _i32, _i32, _f64, _i32, _i64, _p, _p, _p, _p, _p],
 }
 EXPORTS = tuple(_SIGNATURES) + ("anrag_last_error",)
 

@@ -402,4 +402,56 @@ int enqueue_candidates_2k(anrag_index *idx, const CandQuery *q, int32_t n, int32
                           const uint32_t *d_allow_bm25);
 int reserve_call_pool(anrag_index *idx, int64_t bytes, char **out);
 
+// ---- full ranking (rank_batch.hip): the pieces anrag_rank_batch and anrag_shard_group_rank_batch share
+int rank_list_cap(bool fp64);  // anrag_rank_caps
+// one workgroup per segment: the k best of n scores by (score desc, position asc) -> rows, keys (fp64, nullable), counts
+int launch_rank_sort(int device, hipStream_t st, int32_t n_seg, const void *keys, bool fp64, int64_t key_stride, int32_t n,
+                     int32_t k, const int32_t *seg_k, uint32_t *out_rows, double *out_keys, int64_t out_stride,
+                     int32_t *out_count);
+// every map inside [0, id_space) and injective (a NULL map: the leg's rows fit the id space)
+int rank_check_maps(int32_t n_legs, const int64_t *const *maps, const int64_t *leg_rows, int64_t id_space);
+struct RankTailLeg {
+    const uint32_t *rows;       // [chunk][leg_k]
+    const double *row_keys;     // one leg only
+    const int32_t *cnt;         // [chunk]
+    const int32_t *doc_of_row;  // nullable
+    int32_t leg_k;
+    double weight;
+};
+// what runs behind the legs' lists on one device and stream; every pointer is device memory of that device
+struct RankTail {
+    int device = 0;
+    hipStream_t st = nullptr;
+    int n_legs = 0;
+    RankTailLeg leg[ANRAG_WRRF_MAX_LISTS] = {};
+    bool fuse_in_lds = false;
+    double wrrf_k = 0;
+    int64_t id_space = 0;
+    int32_t fuse_n = 0, out_n = 0;
+    double *d_f = nullptr, *d_skey = nullptr;  // fusion in HBM
+    uint32_t *d_t = nullptr, *d_stie = nullptr;
+    int32_t *d_scnt = nullptr;
+    uint64_t *d_fuse_legs = nullptr;           // fusion in LDS: rank_fuse_table's words
+    int64_t *d_out_id = nullptr;
+    double *d_out_score = nullptr;
+    int32_t *d_out_cnt = nullptr;
+    int64_t *d_expect = nullptr;
+    int32_t *d_rank = nullptr;
+};
+void rank_fuse_table(const RankTail &t, uint64_t *tab);  // 6 * ANRAG_WRRF_MAX_LISTS words
+int launch_rank_tail(const RankTail &t, int32_t c, bool want_ids);
+int rank_copy_out(const RankTail &t, int32_t c, int64_t q0, int32_t top_n, int64_t *out_id, double *out_score,
+                  int32_t *out_count, int32_t *out_rank);
+
+// ---- a shard group as the ranked route sees it (shard_group.hip owns the struct)
+struct GroupView {
+    std::mutex *mu;
+    int32_t n;
+    anrag_index *const *shard;
+    const int *device;
+    const int64_t *dense_lo, *bm25_lo;  // n + 1 block bounds
+    bool has_dense, has_bm25, has_dense_src, has_bm25_src;
+};
+GroupView shard_group_view(anrag_shard_group *g);
+
 }  // namespace anrag

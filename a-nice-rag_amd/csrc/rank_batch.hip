@@ -903,6 +903,131 @@ static int launch_seg_sort(int device, hipStream_t st, int32_t n_seg, const KEY 
     return ANRAG_OK;
 }
 
+// ------------------------------------------------------------------ shared with anrag_shard_group_rank_batch
+int rank_list_cap(bool fp64) { return fp64 ? rank_cap<3>() : rank_cap<2>(); }
+
+int launch_rank_sort(int device, hipStream_t st, int32_t n_seg, const void *keys, bool fp64, int64_t key_stride, int32_t n,
+                     int32_t k, const int32_t *seg_k, uint32_t *out_rows, double *out_keys, int64_t out_stride,
+                     int32_t *out_count) {
+    if (fp64)
+        return launch_seg_sort<double, false>(device, st, n_seg, static_cast<const double *>(keys), key_stride, nullptr, 0, n, k,
+                                              seg_k, out_rows, out_keys, out_stride, out_count);
+    return launch_seg_sort<float, false>(device, st, n_seg, static_cast<const float *>(keys), key_stride, nullptr, 0, n, k, seg_k,
+                                         out_rows, out_keys, out_stride, out_count);
+}
+
+int rank_check_maps(int32_t n_legs, const int64_t *const *maps, const int64_t *leg_rows, int64_t id_space) {
+    // a leg must name a document once and inside the id space: the additions of a document then happen in leg
+    // order whatever the thread schedule (rank_accumulate_kernel)
+    std::vector<uint64_t> seen((size_t)((id_space + 63) / 64));
+    for (int l = 0; l < n_legs; ++l) {
+        const int64_t *map = maps[l];
+        if (!map) {  // row r is document r: injective as it stands
+            ANRAG_REQUIRE(leg_rows[l] <= id_space, "leg %d: %lld rows, documents [0, %lld)", l, (long long)leg_rows[l],
+                          (long long)id_space);
+            continue;
+        }
+        std::fill(seen.begin(), seen.end(), 0ull);
+        for (int64_t r = 0; r < leg_rows[l]; ++r) {
+            const int64_t d = map ? map[r] : r;
+            ANRAG_REQUIRE(d >= 0 && d < id_space, "leg %d: row %lld maps to document %lld outside [0, %lld)", l,
+                          (long long)r, (long long)d, (long long)id_space);
+            ANRAG_REQUIRE(!((seen[(size_t)(d >> 6)] >> (d & 63)) & 1ull),
+                          "leg %d: document %lld is named by two rows (the batched fusion needs one row per document)",
+                          l, (long long)d);
+            seen[(size_t)(d >> 6)] |= 1ull << (d & 63);
+        }
+    }
+    return ANRAG_OK;
+}
+
+void rank_fuse_table(const RankTail &t, uint64_t *tab) {
+    constexpr int M = ANRAG_WRRF_MAX_LISTS;
+    memset(tab, 0, 6 * M * sizeof(uint64_t));
+    for (int l = 0; l < t.n_legs; ++l) {
+        tab[l] = reinterpret_cast<uint64_t>(t.leg[l].rows);
+        tab[M + l] = reinterpret_cast<uint64_t>(t.leg[l].cnt);
+        tab[2 * M + l] = reinterpret_cast<uint64_t>(t.leg[l].doc_of_row);
+        tab[3 * M + l] = (uint64_t)t.leg[l].leg_k;
+        memcpy(&tab[4 * M + l], &t.leg[l].weight, 8);
+    }
+    tab[5 * M] = (uint64_t)t.n_legs;
+}
+
+// Fusion and emit of one chunk of c queries, behind the legs' lists (rows, counts; one leg: its keys too).
+int launch_rank_tail(const RankTail &t, int32_t c, bool want_ids) {
+    const int n_legs = t.n_legs;
+    const int32_t out_n = t.out_n;
+    hipStream_t st = t.st;
+    int rc;
+    if (n_legs > 1 && t.fuse_in_lds) {
+        if ((rc = ensure_dynamic_lds(t.device, reinterpret_cast<const void *>(&rank_fuse_sort_kernel), rank_lds_bytes<3>())))
+            return rc;
+        rank_fuse_sort_kernel<<<c, kRankThreads, rank_lds_bytes<3>(), st>>>(
+            t.d_fuse_legs, t.wrrf_k, (int32_t)t.id_space, out_n, want_ids ? t.d_out_id : nullptr, t.d_out_score, t.d_out_cnt,
+            t.d_expect, t.d_rank);
+    } else if (n_legs > 1) {
+        const int64_t id_space = t.id_space;
+        const int64_t total = (int64_t)c * id_space;
+        rank_fill_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(t.d_f, t.d_t, total);
+        RankLegsDev L;
+        for (int l = 0; l < ANRAG_WRRF_MAX_LISTS; ++l) {
+            L.rows[l] = l < n_legs ? t.leg[l].rows : nullptr;
+            L.rows_stride[l] = l < n_legs ? t.leg[l].leg_k : 0;
+            L.doc_of_row[l] = l < n_legs ? t.leg[l].doc_of_row : nullptr;
+        }
+        for (int l = 0; l < n_legs; ++l) {
+            const dim3 grid((unsigned)((t.leg[l].leg_k + 255) / 256), (unsigned)c);
+            rank_accumulate_kernel<<<grid, 256, 0, st>>>(t.leg[l].rows, t.leg[l].leg_k, t.leg[l].cnt, t.leg[l].doc_of_row,
+                                                         (uint32_t)l, t.leg[l].weight, t.wrrf_k, id_space, t.d_f, t.d_t);
+        }
+        ANRAG_HIP(hipGetLastError());
+        if ((rc = launch_seg_sort<double, true>(t.device, st, c, t.d_f, id_space, t.d_t, id_space, (int32_t)id_space, t.fuse_n,
+                                                nullptr, t.d_stie, t.d_skey, t.fuse_n, t.d_scnt)))
+            return rc;
+        const dim3 grid((unsigned)((out_n + 255) / 256), (unsigned)c);
+        rank_emit_fused_kernel<<<grid, 256, 0, st>>>(L, t.d_stie, t.d_skey, t.fuse_n, t.d_scnt, out_n, t.d_out_id,
+                                                     t.d_out_score, t.d_expect, t.d_rank);
+    } else {
+        const dim3 grid((unsigned)((out_n + 255) / 256), (unsigned)c);
+        rank_emit_single_kernel<<<grid, 256, 0, st>>>(t.leg[0].rows, t.leg[0].row_keys, t.leg[0].leg_k, t.leg[0].cnt,
+                                                      t.leg[0].doc_of_row, out_n, t.d_out_id, t.d_out_score, t.d_out_cnt,
+                                                      t.d_expect, t.d_rank);
+    }
+    ANRAG_HIP(hipGetLastError());
+    return ANRAG_OK;
+}
+
+// The chunk's results straight into the caller's arrays and the chunk's one host sync: rows of out_n entries into rows
+// of top_n (the device wrote the -1 / -inf padding of the first out_n columns; columns past out_n, if the caller asked
+// for more, are filled here)
+int rank_copy_out(const RankTail &t, int32_t c, int64_t q0, int32_t top_n, int64_t *out_id, double *out_score,
+                  int32_t *out_count, int32_t *out_rank) {
+    const int32_t out_n = t.out_n;
+    hipStream_t st = t.st;
+    if (out_id)
+        ANRAG_HIP(hipMemcpy2DAsync(out_id + q0 * (int64_t)top_n, (size_t)top_n * 8, t.d_out_id, (size_t)out_n * 8,
+                                   (size_t)out_n * 8, (size_t)c, hipMemcpyDeviceToHost, st));
+    if (out_score)
+        ANRAG_HIP(hipMemcpy2DAsync(out_score + q0 * (int64_t)top_n, (size_t)top_n * 8, t.d_out_score, (size_t)out_n * 8,
+                                   (size_t)out_n * 8, (size_t)c, hipMemcpyDeviceToHost, st));
+    ANRAG_HIP(hipMemcpyAsync(out_count + q0, t.d_out_cnt, (size_t)c * 4, hipMemcpyDeviceToHost, st));
+    if (out_rank) ANRAG_HIP(hipMemcpyAsync(out_rank + q0, t.d_rank, (size_t)c * 4, hipMemcpyDeviceToHost, st));
+    ANRAG_HIP(hipStreamSynchronize(st));  // the chunk's one host sync for results
+    for (int32_t q = 0; q < c; ++q) {
+        if (out_count[q0 + q] > out_n) out_count[q0 + q] = out_n;
+        if (out_n < top_n && out_id) {
+            int64_t *oi = out_id + (q0 + q) * (int64_t)top_n;
+            double *os = out_score ? out_score + (q0 + q) * (int64_t)top_n : nullptr;
+            for (int32_t i = out_n; i < top_n; ++i) {
+                oi[i] = -1;
+                if (os) os[i] = -__builtin_huge_val();
+            }
+        }
+    }
+    return ANRAG_OK;
+}
+
 }  // namespace anrag
 
 using namespace anrag;
@@ -985,27 +1110,9 @@ extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int3
         ANRAG_REQUIRE(fuse_n <= rank_cap<3>(), "min(top_n, entries) = %d is outside the batched ranking's envelope (%d)",
                       fuse_n, rank_cap<3>());
         fuse_in_lds = id_space <= rank_cap<3>() && !getenv("ANRAG_RANK_FUSE_IN_HBM");
-        // a leg must name a document once and inside the id space: the additions of a document then happen in leg
-        // order whatever the thread schedule (rank_accumulate_kernel)
-        std::vector<uint64_t> seen((size_t)((id_space + 63) / 64));
-        for (int l = 0; l < n_legs; ++l) {
-            const int64_t *map = legs[l].doc_of_row;
-            if (!map) {  // row r is document r: injective as it stands
-                ANRAG_REQUIRE(leg_rows[l] <= id_space, "leg %d: %lld rows, documents [0, %lld)", l, (long long)leg_rows[l],
-                              (long long)id_space);
-                continue;
-            }
-            std::fill(seen.begin(), seen.end(), 0ull);
-            for (int64_t r = 0; r < leg_rows[l]; ++r) {
-                const int64_t d = map ? map[r] : r;
-                ANRAG_REQUIRE(d >= 0 && d < id_space, "leg %d: row %lld maps to document %lld outside [0, %lld)", l,
-                              (long long)r, (long long)d, (long long)id_space);
-                ANRAG_REQUIRE(!((seen[(size_t)(d >> 6)] >> (d & 63)) & 1ull),
-                              "leg %d: document %lld is named by two rows (the batched fusion needs one row per document)",
-                              l, (long long)d);
-                seen[(size_t)(d >> 6)] |= 1ull << (d & 63);
-            }
-        }
+        const int64_t *maps[ANRAG_WRRF_MAX_LISTS];
+        for (int l = 0; l < n_legs; ++l) maps[l] = legs[l].doc_of_row;
+        if (int rc = rank_check_maps(n_legs, maps, leg_rows, id_space)) return rc;
     }
     for (anrag_index *o : owners)
         if (int rc = settle_pipeline(o)) return rc;
@@ -1110,17 +1217,31 @@ extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int3
         return ANRAG_ERR_STATE;
     }
 
+    RankTail tail;  // everything behind the legs' lists: the same buffers for every chunk
+    tail.device = device;
+    tail.st = st;
+    tail.n_legs = n_legs;
+    for (int l = 0; l < n_legs; ++l)
+        tail.leg[l] = RankTailLeg{ld[l].rows, ld[l].row_keys, ld[l].cnt, ld[l].doc_of_row, leg_k[l], legs[l].weight};
+    tail.fuse_in_lds = fuse_in_lds;
+    tail.wrrf_k = wrrf_k;
+    tail.id_space = id_space;
+    tail.fuse_n = fuse_n;
+    tail.out_n = out_n;
+    tail.d_f = d_f;
+    tail.d_t = d_t;
+    tail.d_stie = d_stie;
+    tail.d_skey = d_skey;
+    tail.d_scnt = d_scnt;
+    tail.d_fuse_legs = d_fuse_legs;
+    tail.d_out_id = d_out_id;
+    tail.d_out_score = d_out_score;
+    tail.d_out_cnt = d_out_cnt;
+    tail.d_expect = d_expect;
+    tail.d_rank = d_rank;
     if (fuse_in_lds) {  // the legs' lists, counts, maps, strides and weights: the same for every chunk
-        constexpr int M = ANRAG_WRRF_MAX_LISTS;
-        uint64_t tab[6 * M] = {};
-        for (int l = 0; l < n_legs; ++l) {
-            tab[l] = reinterpret_cast<uint64_t>(ld[l].rows);
-            tab[M + l] = reinterpret_cast<uint64_t>(ld[l].cnt);
-            tab[2 * M + l] = reinterpret_cast<uint64_t>(ld[l].doc_of_row);
-            tab[3 * M + l] = (uint64_t)leg_k[l];
-            memcpy(&tab[4 * M + l], &legs[l].weight, 8);
-        }
-        tab[5 * M] = (uint64_t)n_legs;
+        uint64_t tab[6 * ANRAG_WRRF_MAX_LISTS];
+        rank_fuse_table(tail, tab);
         ANRAG_HIP(hipMemcpyAsync(d_fuse_legs, tab, sizeof(tab), hipMemcpyHostToDevice, st));
         ANRAG_HIP(hipStreamSynchronize(st));
     }
@@ -1196,62 +1317,9 @@ extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int3
                     return rc;
             }
         }
-        if (fuse && fuse_in_lds) {
-            if ((rc = ensure_dynamic_lds(device, reinterpret_cast<const void *>(&rank_fuse_sort_kernel), rank_lds_bytes<3>())))
-                return rc;
-            rank_fuse_sort_kernel<<<c, kRankThreads, rank_lds_bytes<3>(), st>>>(
-                d_fuse_legs, wrrf_k, (int32_t)id_space, out_n, out_id ? d_out_id : nullptr, d_out_score, d_out_cnt, d_expect,
-                d_rank);
-        } else if (fuse) {
-            const int64_t total = (int64_t)c * id_space;
-            rank_fill_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(d_f, d_t, total);
-            RankLegsDev L;
-            for (int l = 0; l < ANRAG_WRRF_MAX_LISTS; ++l) {
-                L.rows[l] = l < n_legs ? ld[l].rows : nullptr;
-                L.rows_stride[l] = l < n_legs ? leg_k[l] : 0;
-                L.doc_of_row[l] = l < n_legs ? ld[l].doc_of_row : nullptr;
-            }
-            for (int l = 0; l < n_legs; ++l) {
-                const dim3 grid((unsigned)((leg_k[l] + 255) / 256), (unsigned)c);
-                rank_accumulate_kernel<<<grid, 256, 0, st>>>(ld[l].rows, leg_k[l], ld[l].cnt, ld[l].doc_of_row, (uint32_t)l,
-                                                             legs[l].weight, wrrf_k, id_space, d_f, d_t);
-            }
-            ANRAG_HIP(hipGetLastError());
-            if ((rc = launch_seg_sort<double, true>(device, st, c, d_f, id_space, d_t, id_space, (int32_t)id_space, fuse_n,
-                                                    nullptr, d_stie, d_skey, fuse_n, d_scnt)))
-                return rc;
-            const dim3 grid((unsigned)((out_n + 255) / 256), (unsigned)c);
-            rank_emit_fused_kernel<<<grid, 256, 0, st>>>(L, d_stie, d_skey, fuse_n, d_scnt, out_n, d_out_id, d_out_score,
-                                                         d_expect, d_rank);
-        } else if (!count_only) {
-            const dim3 grid((unsigned)((out_n + 255) / 256), (unsigned)c);
-            rank_emit_single_kernel<<<grid, 256, 0, st>>>(ld[0].rows, ld[0].row_keys, leg_k[0], ld[0].cnt,
-                                                          ld[0].doc_of_row, out_n, d_out_id, d_out_score, d_out_cnt,
-                                                          d_expect, d_rank);
-        }
+        if (!count_only && (rc = launch_rank_tail(tail, c, out_id != nullptr))) return rc;
         ANRAG_HIP(hipGetLastError());
-        // results straight into the caller's arrays: rows of out_n entries into rows of top_n (the device wrote the
-        // -1 / -inf padding of the first out_n columns; columns past out_n, if the caller asked for more, are filled here)
-        if (out_id)
-            ANRAG_HIP(hipMemcpy2DAsync(out_id + q0 * (int64_t)top_n, (size_t)top_n * 8, d_out_id, (size_t)out_n * 8,
-                                       (size_t)out_n * 8, (size_t)c, hipMemcpyDeviceToHost, st));
-        if (out_score)
-            ANRAG_HIP(hipMemcpy2DAsync(out_score + q0 * (int64_t)top_n, (size_t)top_n * 8, d_out_score, (size_t)out_n * 8,
-                                       (size_t)out_n * 8, (size_t)c, hipMemcpyDeviceToHost, st));
-        ANRAG_HIP(hipMemcpyAsync(out_count + q0, d_out_cnt, (size_t)c * 4, hipMemcpyDeviceToHost, st));
-        if (out_rank) ANRAG_HIP(hipMemcpyAsync(out_rank + q0, d_rank, (size_t)c * 4, hipMemcpyDeviceToHost, st));
-        ANRAG_HIP(hipStreamSynchronize(st));  // the chunk's one host sync for results
-        for (int32_t q = 0; q < c; ++q) {
-            if (out_count[q0 + q] > out_n) out_count[q0 + q] = out_n;
-            if (out_n < top_n && out_id) {
-                int64_t *oi = out_id + (q0 + q) * (int64_t)top_n;
-                double *os = out_score ? out_score + (q0 + q) * (int64_t)top_n : nullptr;
-                for (int32_t i = out_n; i < top_n; ++i) {
-                    oi[i] = -1;
-                    if (os) os[i] = -__builtin_huge_val();
-                }
-            }
-        }
+        if ((rc = rank_copy_out(tail, c, q0, top_n, out_id, out_score, out_count, out_rank))) return rc;
     }
     return ANRAG_OK;
 }

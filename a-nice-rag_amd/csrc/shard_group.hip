@@ -168,6 +168,11 @@ struct anrag_shard_group {
     int64_t own_bytes = 0;
 };
 
+anrag::GroupView anrag::shard_group_view(anrag_shard_group *g) {
+    return GroupView{&g->mu, g->n, g->shard, g->device, g->dense_lo, g->bm25_lo,
+                     g->has_dense, g->has_bm25, g->has_dense_src, g->has_bm25_src};
+}
+
 namespace {
 
 constexpr size_t kAllowBytes = 2048 * sizeof(uint32_t);

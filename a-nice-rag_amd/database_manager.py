@@ -35,8 +35,9 @@ def _default_device() -> int:
 
 def _open_index(device: Optional[int] = None):
     """The index a handle holds.  `ANRAG_DEVICES=0,1,...` (repeats allowed), read where the default device is read: a
-    `ShardGroup` over those devices -- one corpus, several GPUs, this process -- instead of one `Index`.  A group that
-    cannot be built raises; nothing falls back to one index."""
+    `ShardGroup` over those devices -- one corpus, several GPUs, this process -- instead of one `Index`.  Every dense
+    model and the BM25 proxy own a group of their own; `index.rank_batch_group` takes them as the legs of one call.  A
+    group that cannot be built raises; nothing falls back to one index."""
     if device is None and os.environ.get("ANRAG_DEVICES") is not None:
         return ShardGroup(parse_devices(os.environ["ANRAG_DEVICES"]))
     return Index(_default_device() if device is None else device)
@@ -115,7 +116,8 @@ class Bm25Proxy:
 
     def get_scores(self, query: Sequence[str]) -> np.ndarray:
         """On a shard group (`ANRAG_DEVICES`) this raises `AnragError` (ANRAG_ERR_UNSUPPORTED): a group serves ranked
-        lists, not score dumps."""
+        lists -- single queries, `hybrid_search_batch` and, for lists of queries in full-ranking mode,
+        `index.rank_batch_group` -- not score dumps."""
         return self.index.bm25_scores(self.term_ids(query))
 
     @classmethod

@@ -31,6 +31,62 @@ def rank_caps() -> Tuple[int, int]:
     return a.value, b.value
 
 
+def _fill_leg(slot, leg: dict, i: int, n_queries: int, keep: list) -> None:
+    """The operands of one leg into its C struct (`RankLeg` / `GroupRankLeg`: the shared fields); `keep` holds the arrays."""
+    ix = leg["index"]
+    slot.weight = float(leg["weight"])
+    allow, ns = _allow_bytes(leg.get("allow"))
+    keep.append(allow)
+    slot.allow_source = nat.ptr(allow)
+    slot.n_sources = ns
+    dmap = leg.get("doc_of_row")
+    if dmap is not None:
+        dmap = np.ascontiguousarray(dmap, dtype=np.int64)
+        keep.append(dmap)
+    slot.doc_of_row = nat.ptr(dmap)
+    if leg.get("queries") is not None:
+        q = _f32(leg["queries"])
+        if q.ndim == 1:
+            q = q[None, :]
+        assert q.shape == (n_queries, ix.dim), f"leg {i}: queries {q.shape} != ({n_queries}, {ix.dim})"
+        keep.append(q)
+        slot.kind = nat.LEG_DENSE
+        slot.queries = q.ctypes.data
+    else:
+        term_lists = leg["term_lists"]
+        assert len(term_lists) == n_queries
+        offsets = np.zeros(n_queries + 1, dtype=np.int64)
+        np.cumsum(np.fromiter(map(len, term_lists), np.int64, n_queries), out=offsets[1:])
+        if not offsets[-1]:
+            terms = np.zeros(1, np.int32)
+        elif all(type(t) is np.ndarray and t.dtype == np.int32 and t.ndim == 1 for t in term_lists):
+            terms = np.concatenate(term_lists)  # (what Bm25Index.term_ids returns: no per-list conversion)
+        else:
+            terms = np.concatenate([np.asarray(t, dtype=np.int32).reshape(-1) for t in term_lists]).astype(np.int32)
+        terms = np.ascontiguousarray(terms)
+        keep += [offsets, terms]
+        slot.kind = nat.LEG_BM25
+        slot.term_ids = terms.ctypes.data
+        slot.term_offsets = offsets.ctypes.data
+
+
+def _rank_call(entry, arr, n_legs, n_queries, similarity_k, wrrf_k, top_n, id_space, want_scores, expect, want_ids):
+    out_id = np.empty((n_queries, top_n), np.int64) if want_ids else None
+    out_score = np.empty((n_queries, top_n), np.float64) if want_scores and want_ids else None
+    count = np.zeros(n_queries, np.int32)
+    exp = ranks = None
+    if expect is not None:
+        exp = np.ascontiguousarray(expect, dtype=np.int64)
+        assert exp.shape == (n_queries,)
+        ranks = np.empty(n_queries, np.int32)
+    nat.check(entry(C.cast(arr, C.c_void_p), n_legs, int(n_queries), int(similarity_k), float(wrrf_k),
+                    int(top_n), int(id_space), nat.ptr(out_id), nat.ptr(out_score),
+                    count.ctypes.data, nat.ptr(exp), nat.ptr(ranks)))
+    if expect is not None:
+        return out_id, out_score, count, ranks
+    return out_id, out_score, count
+
+
 def rank_batch(legs: Sequence[dict], n_queries: int, similarity_k: int, wrrf_k: float, top_n: int,
                id_space: int = 0, want_scores: bool = False, expect=None, want_ids: bool = True):
     """`anrag_rank_batch`: full-ranking retrieval (large k) for a LIST of queries, every step on the device.
@@ -45,56 +101,30 @@ def rank_batch(legs: Sequence[dict], n_queries: int, similarity_k: int, wrrf_k: 
     arr = (nat.RankLeg * len(legs))()
     keep = []
     for i, leg in enumerate(legs):
+        arr[i].idx = leg["index"].handle  # (a ShardGroup has none: ERR_UNSUPPORTED -- its entry is rank_batch_group)
+        _fill_leg(arr[i], leg, i, n_queries, keep)
+    return _rank_call(lib.anrag_rank_batch, arr, len(legs), n_queries, similarity_k, wrrf_k, top_n, id_space, want_scores,
+                      expect, want_ids)
+
+
+def rank_batch_group(legs: Sequence[dict], n_queries: int, similarity_k: int, wrrf_k: float, top_n: int,
+                     id_space: int = 0, want_scores: bool = False, expect=None, want_ids: bool = True):
+    """`anrag_shard_group_rank_batch`: `rank_batch` for legs that live on shard groups -- a leg's `index` is a
+    `ShardGroup` or an `Index`, the legs may sit on different groups, shard counts and devices.  Same arguments, same
+    return shapes, and the same ids, counts, ranks and score bits as `rank_batch` on ONE index holding the whole corpus
+    (`doc_of_row` maps the leg's GLOBAL rows)."""
+    lib = nat.load_library()
+    arr = (nat.GroupRankLeg * len(legs))()
+    keep = []
+    for i, leg in enumerate(legs):
         ix = leg["index"]
-        arr[i].idx = ix.handle
-        arr[i].weight = float(leg["weight"])
-        allow, ns = _allow_bytes(leg.get("allow"))
-        keep.append(allow)
-        arr[i].allow_source = nat.ptr(allow)
-        arr[i].n_sources = ns
-        dmap = leg.get("doc_of_row")
-        if dmap is not None:
-            dmap = np.ascontiguousarray(dmap, dtype=np.int64)
-            keep.append(dmap)
-        arr[i].doc_of_row = nat.ptr(dmap)
-        if leg.get("queries") is not None:
-            q = _f32(leg["queries"])
-            if q.ndim == 1:
-                q = q[None, :]
-            assert q.shape == (n_queries, ix.dim), f"leg {i}: queries {q.shape} != ({n_queries}, {ix.dim})"
-            keep.append(q)
-            arr[i].kind = nat.LEG_DENSE
-            arr[i].queries = q.ctypes.data
+        if isinstance(ix, ShardGroup):
+            arr[i].group = ix.group
         else:
-            term_lists = leg["term_lists"]
-            assert len(term_lists) == n_queries
-            offsets = np.zeros(n_queries + 1, dtype=np.int64)
-            np.cumsum(np.fromiter(map(len, term_lists), np.int64, n_queries), out=offsets[1:])
-            if not offsets[-1]:
-                terms = np.zeros(1, np.int32)
-            elif all(type(t) is np.ndarray and t.dtype == np.int32 and t.ndim == 1 for t in term_lists):
-                terms = np.concatenate(term_lists)  # (what Bm25Index.term_ids returns: no per-list conversion)
-            else:
-                terms = np.concatenate([np.asarray(t, dtype=np.int32).reshape(-1) for t in term_lists]).astype(np.int32)
-            terms = np.ascontiguousarray(terms)
-            keep += [offsets, terms]
-            arr[i].kind = nat.LEG_BM25
-            arr[i].term_ids = terms.ctypes.data
-            arr[i].term_offsets = offsets.ctypes.data
-    out_id = np.empty((n_queries, top_n), np.int64) if want_ids else None
-    out_score = np.empty((n_queries, top_n), np.float64) if want_scores and want_ids else None
-    count = np.zeros(n_queries, np.int32)
-    exp = ranks = None
-    if expect is not None:
-        exp = np.ascontiguousarray(expect, dtype=np.int64)
-        assert exp.shape == (n_queries,)
-        ranks = np.empty(n_queries, np.int32)
-    nat.check(lib.anrag_rank_batch(C.cast(arr, C.c_void_p), len(legs), int(n_queries), int(similarity_k), float(wrrf_k),
-                                   int(top_n), int(id_space), nat.ptr(out_id), nat.ptr(out_score),
-                                   count.ctypes.data, nat.ptr(exp), nat.ptr(ranks)))
-    if expect is not None:
-        return out_id, out_score, count, ranks
-    return out_id, out_score, count
+            arr[i].idx = ix.handle
+        _fill_leg(arr[i], leg, i, n_queries, keep)
+    return _rank_call(lib.anrag_shard_group_rank_batch, arr, len(legs), n_queries, similarity_k, wrrf_k, top_n, id_space,
+                      want_scores, expect, want_ids)
 
 
 def parse_devices(text: str) -> list:
@@ -119,8 +149,9 @@ def group_bounds(n: int, n_shards: int) -> list:
 class ShardGroup:
     """Owns an `anrag_shard_group*`: ONE corpus over several GPUs (or several shards of one GPU) in one process, with
     `Index`'s method names and return shapes for what a group serves -- every answer equals the single index's, ids,
-    counts and score bits.  `dense_scores`, `bm25_scores` and the ranking route (`rank_batch` takes `Index` legs: a
-    group has no `handle`) raise `AnragError` with code `ERR_UNSUPPORTED`."""
+    counts and score bits.  Ranked lists of queries (full ranking) go through `rank_batch_group`.  `dense_scores`,
+    `bm25_scores` and `rank_batch` itself (it takes `Index` legs: a group has no `handle`) raise `AnragError` with code
+    `ERR_UNSUPPORTED`."""
 
     def __init__(self, devices: Sequence[int]):
         self._lib = nat.load_library()
@@ -160,8 +191,9 @@ class ShardGroup:
 
     @property
     def handle(self):
-        raise nat.AnragError(nat.ERR_UNSUPPORTED, "a shard group has no anrag_index handle: the ranking route "
-                                                  "(anrag_rank_batch) and the *_device entries take one index")
+        raise nat.AnragError(nat.ERR_UNSUPPORTED, "a shard group has no anrag_index handle: anrag_rank_batch "
+                                                  "(a group's entry is rank_batch_group) and the *_device entries take "
+                                                  "one index")
 
     def shard(self, i: int) -> C.c_void_p:
         """Borrowed `anrag_index*` of shard i (stats, profiling, tests); it dies with the group."""

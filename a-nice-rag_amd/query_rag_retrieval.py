@@ -253,8 +253,10 @@ class RetrievalEvaluationSystem:
     # ------------------------------------------------------------------ query lists
     @staticmethod
     def _on_shard_group(embeddings_dict, bm25) -> bool:
-        """True when a frame of this info source, or its BM25 proxy, lives on a `ShardGroup`: lists of queries then go
-        through `hybrid_search_batch` (the pipelined batch = 1 kernels) or query by query (large k: the cold routes)."""
+        """True when a frame of this info source, or its BM25 proxy, lives on a `ShardGroup`: small-k lists of queries
+        then go through `hybrid_search_batch` (the pipelined batch = 1 kernels), ranked lists (large k and the other
+        ids-only requests) through `rank_batch_group`; the rank-of-expected form is not served (the caller asks for the
+        lists)."""
         from .database_manager import ATTR
         from .index import ShardGroup
 
@@ -271,7 +273,7 @@ class RetrievalEvaluationSystem:
         query) -> (ranks, totals): the 1-based rank of the expected id in each answer (-1: absent; retrieval_eval.py:75-82)
         and the answers' lengths, without materialising the lists.  None = outside this route (the caller answers
         query by query)."""
-        from .index import rank_batch
+        from .index import rank_batch, rank_batch_group
 
         if not queries or not self.fused or params.get("return_docs"):
             return None
@@ -295,8 +297,11 @@ class RetrievalEvaluationSystem:
         bm25_tuple = self.bm25_data.get(source_enum)
         bm25, bm25_sections, bm25_section_ids = bm25_tuple if bm25_tuple else (None, [], [])
         want_bm25 = bool(params.get("use_hybrid_search", False)) and bm25 is not None and model_weights.get("BM25", 0) > 0
-        if self._on_shard_group(embeddings_dict, bm25):
-            return None  # a shard group (ANRAG_DEVICES) does not serve anrag_rank_batch: skipped up front, not tried and caught
+        on_group = self._on_shard_group(embeddings_dict, bm25)
+        if on_group:  # a shard group (ANRAG_DEVICES): the lists through anrag_shard_group_rank_batch; ranks only are not served
+            if expected is not None:
+                return None
+            rank_batch = rank_batch_group
         if params.get("use_reranker", True) and any(q.get("query_text") for q in queries):
             return None  # reranking materialises documents: per query
         from .database_manager import DenseHandle
@@ -409,7 +414,9 @@ class RetrievalEvaluationSystem:
             return one_by_one()
         if similarity_k > 64:
             return ranked()
-        if len(queries) >= self.RANKED_LIST_MIN:
+        if len(queries) >= self.RANKED_LIST_MIN and not self._on_shard_group(embeddings_dict, bm25_tuple[0]):
+            # (not on a shard group: small-k lists stay on its `hybrid_search_batch`; tiles + merge across shards are
+            # unmeasured at small k)
             # A LIST of small-k queries is also served best by the ranking route: its score tiles read the corpus once
             # per 16 queries, the pipeline once per query (9,609 x 384, k = 25: 2.0 against 11.0 us per query; 100k x 768:
             # 7.9 against 45.5) -- same lists, same fused scores (the tiles are bit-identical to the single-query scan).

@@ -500,8 +500,12 @@ int anrag_debug_prefilter_bounds(anrag_index *idx, const float *queries, int32_t
  * nothing (anrag_debug_alloc_calls).
  * Cold routes (k > ANRAG_FUSED_K_MAX, the fp64 query): the shards' host entry points one after the other and a stable
  * merge of their lists on the host.  Serial and untuned on purpose.
- * Not served: anrag_rank_batch and the K2 batched pass (a rank leg takes an anrag_index), the *_device entries, the
- * score dumps: there is no group entry for them; a binding reports ANRAG_ERR_UNSUPPORTED (a-nice-rag_amd/index.py).
+ * Ranked route (lists of queries, full ranking: anrag_shard_group_rank_batch below): every shard runs the score tiles and
+ * the per-query sort of anrag_rank_batch over its own rows; the home device merges the shards' sorted lists stably in
+ * shard order and runs the single index's fusion and emit.
+ * Not served: anrag_rank_batch itself and the K2 batched pass (a rank leg takes an anrag_index), the ranking route of
+ * anrag_hybrid_search_batch, the *_device entries, the score dumps: there is no group entry for them; a binding
+ * reports ANRAG_ERR_UNSUPPORTED (a-nice-rag_amd/index.py).
  * A group is serialised by its own mutex for the whole call. */
 #define ANRAG_GROUP_MAX_SHARDS 16
 typedef struct anrag_shard_group anrag_shard_group;
@@ -548,6 +552,37 @@ int anrag_shard_group_shard(anrag_shard_group *g, int32_t i, anrag_index **out);
  * but including the shards' host-side back-pressure: in a GPU-bound run it reads the GPU's time per group, and the
  * host's own cost only where the GPU never holds the host back.  scripts/measure_shard_group.py. */
 int anrag_shard_group_debug_enqueue(anrag_shard_group *g, int64_t *out_groups, int64_t *out_ns);
+
+/* anrag_rank_batch across shards: for the same operands it returns what anrag_rank_batch returns on ONE index loaded
+ * with the whole corpus -- ids, counts, ranks and score bits.  A leg is a whole group (`group`) or one index (`idx`, e.g.
+ * a model that is not sharded); exactly one of the two is set.  The legs of a call may sit on different groups, with
+ * different shard counts, and on different devices.  doc_of_row is the map of the leg's GLOBAL rows.  The envelope is
+ * anrag_rank_caps applied to the global lists: min(similarity_k, global rows) <= 16384 for a dense leg, <= 13312 for a
+ * BM25 leg, the fused cut <= 13312; outside it ANRAG_ERR_INVALID.
+ * Per chunk of queries and leg, shard s runs the score tiles and the per-query sort (k_s = min(similarity_k, its rows))
+ * on its own primary stream out of its own grow-only scratch and records an event; the home device (leg 0's shard 0)
+ * waits for the events on its stream, merges the S sorted lists of every query with ONE kernel per leg -- score desc,
+ * among equal scores the earlier shard, then the earlier position: (score desc, global row asc) -- and runs the single
+ * index's fusion and emit on the merged lists.  Peer lists are read in place where the home device can map them, else
+ * staged with hipMemcpyPeerAsync.  One host sync per chunk; the steady state allocates nothing.
+ * One leg with out_id == NULL: anrag_rank_batch counts instead of sorting; here the lists are formed all the same and
+ * the rank is read from them (same ranks and counts).
+ * ANRAG_RANK_CHUNK_BUDGET (bytes, measurements and tests only) replaces the 6 GiB of scratch a chunk may take. */
+typedef struct anrag_group_rank_leg {
+    anrag_shard_group *group;
+    anrag_index *idx;
+    int32_t kind; /* ANRAG_LEG_DENSE | ANRAG_LEG_BM25 */
+    const float *queries;
+    const int32_t *term_ids;
+    const int64_t *term_offsets;
+    const uint8_t *allow_source;
+    int32_t n_sources;
+    const int64_t *doc_of_row;
+    double weight;
+} anrag_group_rank_leg;
+int anrag_shard_group_rank_batch(const anrag_group_rank_leg *legs, int32_t n_legs, int32_t n_queries,
+                                 int32_t similarity_k, double wrrf_k, int32_t top_n, int64_t id_space, int64_t *out_id,
+                                 double *out_score, int32_t *out_count, const int64_t *expect_id, int32_t *out_rank);
 
 #ifdef __cplusplus
 }
