@@ -119,6 +119,8 @@ _SIGNATURES = {
     "anrag_shard_group_bm25_search": [_p, _p, _i32, _i32, _p, _i32, _p, _p, _p],
     "anrag_shard_group_debug_enqueue": [_p, C.POINTER(_i64), C.POINTER(_i64)],
     "anrag_shard_group_set_dense_prefilter": [_p, _i32],
+    "anrag_shard_group_set_batched_precision": [_p, _i32],
+    "anrag_shard_group_batched_stats": [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
     "anrag_shard_group_sync": [_p],
     "anrag_shard_group_info": [_p, C.POINTER(_i32), _p, _p, C.POINTER(_i64)],
     "anrag_shard_group_shard": [_p, _i32, C.POINTER(_p)],

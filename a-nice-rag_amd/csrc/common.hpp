@@ -363,6 +363,7 @@ int dense_search_f64(anrag_index *idx, hipStream_t st, const double *h_query, in
 bool batched_path_applies(const anrag_index *idx, int32_t n_queries, int32_t k);
 int launch_dense_batched(anrag_index *idx, hipStream_t st, const float *d_queries, int32_t nq, int32_t k,
                          const uint32_t *d_allow_bits, anrag_candidate *d_out, int32_t *d_flag);
+int reserve_dense_batched(anrag_index *idx, hipStream_t st, int32_t nq, int32_t k);  // its workspace, ahead of the pass
 void free_batched(anrag_index *idx);
 // k > ANRAG_FUSED_K_MAX: score array + radix sort (select.hip); host operands, syncs.
 int dense_search_large_k(anrag_index *idx, hipStream_t stream, const float *h_queries, int32_t n_queries, int32_t k,

@@ -314,12 +314,16 @@ bool batched_path_applies(const anrag_index *idx, int32_t n_queries, int32_t k) 
            idx->n_rows < 0xffffffffLL;  // survivor records carry 32-bit rows
 }
 
-static int ensure_batched_workspace(anrag_index *idx, int64_t n_sample /* floats per query */) {
+static int ensure_batched_workspace(anrag_index *idx, hipStream_t st, int64_t n_sample /* floats per query */) {
     if (!idx->d_bq) {
         ANRAG_HIP(counted_malloc(reinterpret_cast<void **>(&idx->d_bq), (size_t)kBQ * idx->dim * sizeof(float)));
         ANRAG_HIP(counted_malloc(reinterpret_cast<void **>(&idx->d_btau), kBQ * sizeof(float)));
         ANRAG_HIP(counted_malloc(reinterpret_cast<void **>(&idx->d_bcnt), kBQ * sizeof(int32_t)));
-        ANRAG_HIP(hipMemset(idx->d_bcnt, 0, kBQ * sizeof(int32_t)));  // the counters of padding queries are never reset
+        // the counters of padding queries are never reset.  On the pass's own stream: hipMemset fills device memory on the
+        // null stream and may return before the fill has run, the index's streams are non-blocking, and with another
+        // index's pass in flight (a shard group) the fill can queue behind it and zero the counters in the middle of
+        // this index's first full pass ("A first-use hazard")
+        ANRAG_HIP(hipMemsetAsync(idx->d_bcnt, 0, kBQ * sizeof(int32_t), st));
         ANRAG_HIP(counted_malloc(reinterpret_cast<void **>(&idx->d_bflag), kBQ * sizeof(int32_t)));
         ANRAG_HIP(counted_malloc(reinterpret_cast<void **>(&idx->d_bcand), (size_t)kBQ * kCandCap * sizeof(Cand32)));
         idx->hbm_bytes += (int64_t)kBQ * idx->dim * 4 + (int64_t)kBQ * kCandCap * 8;
@@ -404,13 +408,9 @@ static int batched_passes(anrag_index *idx, hipStream_t st, int32_t nq, int32_t 
     return ANRAG_OK;
 }
 
-// One pass of up to 256 queries (device pointers); d_out: nq x k records, d_flag: nq ints (0 ok, -1 redo).
-int launch_dense_batched(anrag_index *idx, hipStream_t st, const float *d_queries, int32_t nq, int32_t k,
-                         const uint32_t *d_allow_bits, anrag_candidate *d_out, int32_t *d_flag) {
-    ANRAG_REQUIRE(nq >= 1 && nq <= kBQ, "a batched pass takes 1..%d queries", kBQ);
+// rows the sampled pass of nq queries visits
+static int64_t batched_sample_rows(const anrag_index *idx, int32_t nq, int32_t k) {
     const int64_t n = idx->n_rows;
-    const int dim = idx->dim;
-    const uint32_t *allow = idx->d_dense_src ? d_allow_bits : nullptr;
     // Sample size.  A score survives the full pass when it reaches the k-th best of the S sampled rows: N*k/S expected
     // survivors per query.  The sampled pass costs ~1 ns per row (beyond the ~64k rows that merely fill the CUs), a
     // survivor ~0.8 ns x 256 queries: the sum is smallest near S = sqrt(128 N k) (36k rows, ~280 survivors per query at
@@ -430,8 +430,26 @@ int launch_dense_batched(anrag_index *idx, hipStream_t st, const float *d_querie
     const int64_t round_rows = idx->batched_split ? (int64_t)idx->n_cus * 256 : (int64_t)idx->n_cus * kBM / (nq > 128 ? 2 : 1);
     const int64_t filled = (n_sample + round_rows - 1) / round_rows * round_rows;
     if (filled <= n / 8) n_sample = filled;
+    return n_sample;
+}
+
+// The workspace of a pass of nq queries, ahead of it: a caller that keeps passes in flight (shard_group.hip) asks for
+// every pass size of its call first, so that no launch_dense_batched below replaces the sample buffer under a running pass.
+int reserve_dense_batched(anrag_index *idx, hipStream_t st, int32_t nq, int32_t k) {
+    ANRAG_REQUIRE(nq >= 1 && nq <= kBQ, "a batched pass takes 1..%d queries", kBQ);
+    return ensure_batched_workspace(idx, st, sample_floats_per_query(batched_sample_rows(idx, nq, k), idx->batched_split ? 256 : kBM));
+}
+
+// One pass of up to 256 queries (device pointers); d_out: nq x k records, d_flag: nq ints (0 ok, -1 redo).
+int launch_dense_batched(anrag_index *idx, hipStream_t st, const float *d_queries, int32_t nq, int32_t k,
+                         const uint32_t *d_allow_bits, anrag_candidate *d_out, int32_t *d_flag) {
+    ANRAG_REQUIRE(nq >= 1 && nq <= kBQ, "a batched pass takes 1..%d queries", kBQ);
+    const int64_t n = idx->n_rows;
+    const int dim = idx->dim;
+    const uint32_t *allow = idx->d_dense_src ? d_allow_bits : nullptr;
+    const int64_t n_sample = batched_sample_rows(idx, nq, k);
     const int64_t stride = n / n_sample;
-    int rc = ensure_batched_workspace(idx, sample_floats_per_query(n_sample, idx->batched_split ? 256 : kBM));
+    int rc = ensure_batched_workspace(idx, st, sample_floats_per_query(n_sample, idx->batched_split ? 256 : kBM));
     if (rc) return rc;
     // zero-padded query block
     ANRAG_HIP(hipMemsetAsync(idx->d_bq, 0, (size_t)kBQ * dim * sizeof(float), st));

@@ -12,6 +12,7 @@
 // equal BM25 scores (zeros) are common, so a doc-id tie-break would return other ids than the single index.
 #include <algorithm>
 #include <chrono>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -138,6 +139,83 @@ __global__ __launch_bounds__(128) void group_tail_kernel(GroupTailArgs a) {
     wrrf_in_block(s_id, s_c, s_score, s_owner, &s_distinct, 2 * k, a.top_n, out, count);
 }
 
+// ---- dense query LISTS: every shard runs the single index's K2 pass (dense_batched.hip) over its rows, the home device
+// merges the shards' k records per query.  A K2 score is the accumulator of one (corpus row, query) element: its k-steps
+// and the order inside them do not depend on the row's tile, on its place in the tile or on the 128 / 256-query geometry,
+// so a row scores the same bits in its shard as in the whole corpus, and the merged answer is the single index's.
+constexpr int kBatchedQueries = 256;  // queries per chunk: one K2 pass per shard
+constexpr int kBatchedBlocks = 2;     // result blocks per shard: the next chunk's pass runs under this chunk's merge
+
+struct BatchedMergeArgs {
+    const anrag_candidate *list[ANRAG_GROUP_MAX_SHARDS];  // shard s: [n_queries][k], (score desc, row asc), empty (doc -1) last
+    const int32_t *flag[ANRAG_GROUP_MAX_SHARDS];          // shard s: [n_queries], nonzero = its survivor list overflowed
+    int32_t n_shards, k;
+    anrag_candidate *out;  // [n_queries][k]
+    int32_t *count;        // [n_queries]
+    int32_t *out_flag;     // [n_queries]: the OR of the shards' flags
+};
+
+// order-preserving bits of a score, as the list kernels compare them (shard_group_rank.hip): -0.0 == +0.0
+__device__ __forceinline__ uint64_t score_order_bits(double v) {
+    uint64_t b = (uint64_t)__double_as_longlong(v);
+    if ((b << 1) == 0) b = 0;
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+// A wave per query: lane p owns entry p of every shard's list.  The keys of all S lists go to LDS; entry p of shard s
+// then lands at  p + sum over t < s of #{keys of t >= mine} + sum over t > s of #{keys of t > mine}  -- a later shard's
+// candidate gets ahead of an earlier shard's only on a strictly greater score: (score desc, global row asc).  Each term is
+// a binary search over a sorted list; the ranks of the real entries are a permutation, so every output slot has one
+// writer (the slots past the last real entry: the lanes of that number) and nothing is atomic.
+__global__ __launch_bounds__(kWave) void group_batched_merge_kernel(BatchedMergeArgs a) {
+    __shared__ uint64_t s_key[ANRAG_GROUP_MAX_SHARDS * kListLen];
+    __shared__ int32_t s_n[ANRAG_GROUP_MAX_SHARDS];
+    const int lane = threadIdx.x, k = a.k;
+    const int64_t q = blockIdx.x, at = q * k + lane;
+    int32_t total = 0, flagged = 0;
+    for (int s = 0; s < a.n_shards; ++s) {
+        const anrag_candidate c = load_record(a.list[s] + at, lane < k);
+        s_key[s * kListLen + lane] = score_order_bits(c.score);
+        const int32_t n = __builtin_popcountll(__ballot(c.doc >= 0));  // empty entries are the list's tail
+        if (lane == 0) s_n[s] = n;
+        total += n;
+        flagged |= a.flag[s][q];
+    }
+    __syncthreads();
+    anrag_candidate *out = a.out + q * k;
+    for (int s = 0; s < a.n_shards; ++s) {
+        if (lane >= s_n[s]) continue;
+        const uint64_t x = s_key[s * kListLen + lane];
+        int32_t r = lane;
+        for (int t = 0; t < a.n_shards && r < k; ++t) {
+            if (t == s) continue;
+            // entries of t ahead of mine; more than k - r of them put mine outside the answer, so the search stops there
+            const int32_t n_t = s_n[t], room = k - r;
+            int32_t lo = 0, hi = n_t < room ? n_t : room;
+            const uint64_t *kt = s_key + t * kListLen;
+            const bool strict = t > s;  // a later shard stays behind an equal score
+            while (lo < hi) {
+                const int32_t mid = (lo + hi) >> 1;
+                const uint64_t u = kt[mid];
+                if (strict ? u > x : u >= x) lo = mid + 1;
+                else hi = mid;
+            }
+            r += lo;
+        }
+        if (r < k) out[r] = load_record(a.list[s] + at, true);
+    }
+    if (lane < k && lane >= total) {
+        anrag_candidate c;
+        c.score = -__builtin_huge_val();
+        c.doc = -1;
+        out[lane] = c;
+    }
+    if (lane == 0) {
+        a.count[q] = total < k ? total : k;
+        a.out_flag[q] = flagged ? -1 : 0;
+    }
+}
+
 }  // namespace anrag
 
 using namespace anrag;
@@ -166,6 +244,14 @@ struct anrag_shard_group {
     char *h_pin = nullptr;
     float *h_query = nullptr;
     int64_t own_bytes = 0;
+    // the batched dense route (run_batched): the result blocks live in the shards' call pools; here the events, the copy
+    // of an unmappable shard's blocks on the home device, the pinned query chunks, the counters
+    bool batched_on = true;                                                  // ANRAG_GROUP_BATCHED, read at create
+    hipEvent_t ev_pass[ANRAG_GROUP_MAX_SHARDS][kBatchedBlocks] = {};         // shard i's pass has filled the block
+    hipEvent_t ev_merged[kBatchedBlocks] = {};                               // the home stream has read the block
+    char *d_bstage[ANRAG_GROUP_MAX_SHARDS] = {};
+    float *h_bq = nullptr;                                                   // [kBatchedBlocks][kBatchedQueries][dim]
+    int64_t b_passes = 0, b_queries = 0, b_redone = 0;
 };
 
 anrag::GroupView anrag::shard_group_view(anrag_shard_group *g) {
@@ -180,6 +266,13 @@ constexpr size_t kPinTerms = 2 * kAllowBytes;
 constexpr size_t kPinOut = kPinTerms + kGroupTermsMax * sizeof(int32_t);
 constexpr size_t kPinCount = kPinOut + (size_t)kGroupChunk * 2 * kListLen * sizeof(anrag_candidate);
 constexpr size_t kPinBytes = kPinCount + (size_t)kGroupChunk * sizeof(int32_t);
+// the batched dense route's chunks come back through the hot route's result region: per block k records, a count and a
+// flag per query (the two routes never run at the same time)
+constexpr size_t kPinBlock = (size_t)kBatchedQueries * (kListLen * sizeof(anrag_candidate) + 2 * sizeof(int32_t));
+static_assert(kPinOut + kBatchedBlocks * kPinBlock <= kPinBytes, "the batched route's blocks fit the pinned result region");
+// an unmappable shard's block on the home device: records at 0, flags behind them (sized for k = kListLen)
+constexpr size_t kStageFlags = (size_t)kBatchedQueries * kListLen * sizeof(anrag_candidate);
+constexpr size_t kStageBlock = kStageFlags + kBatchedQueries * sizeof(int32_t);
 
 void shard_bounds(int64_t n, int32_t S, int64_t *lo) {
     const int64_t base = n / S, extra = n % S;
@@ -200,16 +293,23 @@ void destroy(anrag_shard_group *g) {
         DeviceGuard guard(g->device[i]);
         for (hipEvent_t e : g->ev_cand[i])
             if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : g->ev_pass[i])
+            if (e) (void)hipEventDestroy(e);
         if (g->d_block[i]) (void)counted_free(g->d_block[i]);
     }
     {
         DeviceGuard guard(g->device[0]);
         for (hipEvent_t e : g->ev_tail)
             if (e) (void)hipEventDestroy(e);
-        for (int32_t i = 0; i < g->n; ++i)
+        for (hipEvent_t e : g->ev_merged)
+            if (e) (void)hipEventDestroy(e);
+        for (int32_t i = 0; i < g->n; ++i) {
             if (g->d_stage[i]) (void)counted_free(g->d_stage[i]);
+            if (g->d_bstage[i]) (void)counted_free(g->d_bstage[i]);
+        }
         if (g->h_pin) (void)counted_host_free(g->h_pin);
         if (g->h_query) (void)counted_host_free(g->h_query);
+        if (g->h_bq) (void)counted_host_free(g->h_bq);
     }
     for (int32_t i = 0; i < g->n; ++i)
         if (g->shard[i]) (void)anrag_index_destroy(g->shard[i]);
@@ -399,6 +499,172 @@ int run_hot(anrag_shard_group *g, const HotCall &c, std::vector<anrag_candidate>
     return ANRAG_OK;
 }
 
+// The batched dense route: a list of queries through K2 on every shard (the caller has checked the single index's gate on
+// each of them).  Per chunk of up to 256 queries: the queries go up from pinned staging on every shard's primary stream,
+// launch_dense_batched follows on that stream into result block (chunk & 1) of the shard's call pool, an event marks the
+// block full; the home stream -- shard 0's primary -- waits for the events, merges (group_batched_merge_kernel; one shard:
+// its block IS the answer) and copies the chunk to pinned memory.  The host enqueues chunk c + 1 before it waits for
+// chunk c.  A pass that fills a block again waits, on the device, for the event behind the home stream's last read of it
+// (with two blocks the host's own wait for chunk c already precedes the enqueue of chunk c + 2; the device wait keeps the
+// rule local to the block).  `redo`: the queries a shard flagged (its survivor list overflowed) -- the caller answers
+// them through the hot route once nothing of this one is in flight.
+int run_batched(anrag_shard_group *g, const float *queries, int32_t n_queries, int32_t k, const uint8_t *allow_source,
+                int32_t n_sources, int64_t *out_doc, float *out_score, int32_t *out_count, std::vector<int32_t> &redo) {
+    const int32_t S = g->n, dim = g->dim;
+    int rc;
+    if (allow_source && (rc = stage_bits(allow_source, n_sources, reinterpret_cast<uint32_t *>(g->h_pin)))) return rc;
+    // the shards' own locks, in address order (shard_group_rank.hip): their workspaces and profiling state are also
+    // reached through the borrowed handles
+    std::vector<anrag_index *> owners(g->shard, g->shard + S);
+    std::sort(owners.begin(), owners.end());
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (anrag_index *o : owners) locks.emplace_back(o->mu);
+
+    float *d_q[ANRAG_GROUP_MAX_SHARDS] = {};
+    anrag_candidate *d_rec[ANRAG_GROUP_MAX_SHARDS][kBatchedBlocks] = {};
+    int32_t *d_flag[ANRAG_GROUP_MAX_SHARDS][kBatchedBlocks] = {};
+    anrag_candidate *d_out = nullptr;
+    int32_t *d_cnt = nullptr, *d_oflag = nullptr;
+    const int32_t n_chunks = (n_queries + kBatchedQueries - 1) / kBatchedQueries;
+    const int32_t tail_nq = n_queries - (n_chunks - 1) * kBatchedQueries;  // the last chunk's queries
+    auto setup = [&](int32_t i) -> int {
+        anrag_index *sh = g->shard[i];
+        DeviceGuard guard(g->device[i]);
+        if (!guard.ok) {
+            set_error("hipSetDevice(%d) failed", g->device[i]);
+            return ANRAG_ERR_HIP;
+        }
+        if ((rc = settle_pipeline(sh))) return rc;
+        Carver measure(nullptr), *cv = &measure;
+        auto carve = [&]() {
+            d_q[i] = cv->take<float>((int64_t)kBatchedQueries * dim);
+            for (int b = 0; b < kBatchedBlocks; ++b) {
+                d_rec[i][b] = cv->take<anrag_candidate>((int64_t)kBatchedQueries * k);
+                d_flag[i][b] = cv->take<int32_t>(kBatchedQueries);
+            }
+            if (i == 0 && S > 1) {
+                d_out = cv->take<anrag_candidate>((int64_t)kBatchedQueries * k);
+                d_cnt = cv->take<int32_t>(kBatchedQueries);
+                d_oflag = cv->take<int32_t>(kBatchedQueries);
+            }
+        };
+        carve();
+        if ((rc = ensure_pool(sh, sh->call_pool, measure.at + 256))) return rc;  // grow-only; nothing of the shard's is in flight
+        Carver real(sh->call_pool.p);
+        cv = &real;
+        carve();
+        // K2's workspace for both pass sizes of the call (the sample grows when a pass has 128 queries or fewer): sized
+        // here, where nothing is in flight, so that no pass replaces it under the one before
+        if (n_chunks > 1 && (rc = reserve_dense_batched(sh, sh->primary, kBatchedQueries, k))) return rc;
+        if ((rc = reserve_dense_batched(sh, sh->primary, tail_nq, k))) return rc;
+        if (allow_source)
+            ANRAG_HIP(hipMemcpyAsync(g->d_allow_a[i], g->h_pin, kAllowBytes, hipMemcpyHostToDevice, sh->primary));
+        return ANRAG_OK;
+    };
+    hipStream_t home = g->shard[0]->primary;
+    auto pin_rec = [&](int b) { return reinterpret_cast<anrag_candidate *>(g->h_pin + kPinOut + b * kPinBlock); };
+    auto pin_cnt = [&](int b) { return reinterpret_cast<int32_t *>(pin_rec(b) + (size_t)kBatchedQueries * kListLen); };
+    auto pin_flag = [&](int b) { return pin_cnt(b) + kBatchedQueries; };
+
+    auto enqueue = [&](int32_t c) -> int {
+        const int b = c % kBatchedBlocks;
+        const int32_t q0 = c * kBatchedQueries, nq = std::min(kBatchedQueries, n_queries - q0);
+        float *h_q = g->h_bq + (size_t)b * kBatchedQueries * dim;  // free: the host has waited for chunk c - 2
+        memcpy(h_q, queries + (int64_t)q0 * dim, (size_t)nq * dim * sizeof(float));
+        for (int32_t i = 0; i < S; ++i) {
+            anrag_index *sh = g->shard[i];
+            DeviceGuard guard(g->device[i]);
+            // (the home shard's own stream orders its pass behind the merge that read the block)
+            if (i > 0) ANRAG_HIP(hipStreamWaitEvent(sh->primary, g->ev_merged[b], 0));
+            ANRAG_HIP(hipMemcpyAsync(d_q[i], h_q, (size_t)nq * dim * sizeof(float), hipMemcpyHostToDevice, sh->primary));
+            if (int r = launch_dense_batched(sh, sh->primary, d_q[i], nq, k, allow_source ? g->d_allow_a[i] : nullptr,
+                                             d_rec[i][b], d_flag[i][b]))
+                return r;
+            if (i > 0) ANRAG_HIP(hipEventRecord(g->ev_pass[i][b], sh->primary));
+        }
+        DeviceGuard guard(g->device[0]);
+        const anrag_candidate *src_rec = d_rec[0][b];
+        const int32_t *src_cnt = nullptr, *src_flag = d_flag[0][b];
+        if (S > 1) {
+            BatchedMergeArgs a;
+            for (int32_t i = 0; i < ANRAG_GROUP_MAX_SHARDS; ++i) {
+                a.list[i] = d_rec[0][b];
+                a.flag[i] = d_flag[0][b];
+            }
+            for (int32_t i = 1; i < S; ++i) {
+                ANRAG_HIP(hipStreamWaitEvent(home, g->ev_pass[i][b], 0));  // the device waits, not the host
+                if (g->in_place[i]) {
+                    a.list[i] = d_rec[i][b];
+                    a.flag[i] = d_flag[i][b];
+                } else {
+                    char *st = g->d_bstage[i] + b * kStageBlock;
+                    ANRAG_HIP(hipMemcpyPeerAsync(st, g->device[0], d_rec[i][b], g->device[i],
+                                                 (size_t)nq * k * sizeof(anrag_candidate), home));
+                    ANRAG_HIP(hipMemcpyPeerAsync(st + kStageFlags, g->device[0], d_flag[i][b], g->device[i],
+                                                 (size_t)nq * sizeof(int32_t), home));
+                    a.list[i] = reinterpret_cast<const anrag_candidate *>(st);
+                    a.flag[i] = reinterpret_cast<const int32_t *>(st + kStageFlags);
+                }
+            }
+            a.n_shards = S;
+            a.k = k;
+            a.out = d_out;
+            a.count = d_cnt;
+            a.out_flag = d_oflag;
+            {
+                LaunchTimer t(g->shard[0], ANRAG_KERNEL_SELECT, home, nq);
+                group_batched_merge_kernel<<<nq, kWave, 0, home>>>(a);
+                ANRAG_HIP(hipGetLastError());
+            }
+            src_rec = d_out;
+            src_cnt = d_cnt;
+            src_flag = d_oflag;
+        }
+        ANRAG_HIP(hipMemcpyAsync(pin_rec(b), src_rec, (size_t)nq * k * sizeof(anrag_candidate), hipMemcpyDeviceToHost, home));
+        if (src_cnt) ANRAG_HIP(hipMemcpyAsync(pin_cnt(b), src_cnt, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, home));
+        ANRAG_HIP(hipMemcpyAsync(pin_flag(b), src_flag, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost, home));
+        ANRAG_HIP(hipEventRecord(g->ev_merged[b], home));
+        return ANRAG_OK;
+    };
+    auto run = [&]() -> int {
+        for (int32_t i = 0; i < S; ++i)
+            if (int r = setup(i)) return r;
+        if (int r = enqueue(0)) return r;
+        for (int32_t c = 0; c < n_chunks; ++c) {
+            if (c + 1 < n_chunks)
+                if (int r = enqueue(c + 1)) return r;
+            const int b = c % kBatchedBlocks;
+            const int32_t q0 = c * kBatchedQueries, nq = std::min(kBatchedQueries, n_queries - q0);
+            {   // the chunk's one host wait: by the event chain it follows every shard's pass of the chunk
+                DeviceGuard guard(g->device[0]);
+                ANRAG_HIP(hipEventSynchronize(g->ev_merged[b]));
+            }
+            const anrag_candidate *rec = pin_rec(b);
+            for (int32_t qi = 0; qi < nq; ++qi) {
+                int32_t cnt = 0;
+                for (int32_t j = 0; j < k; ++j) {
+                    const anrag_candidate &r = rec[(size_t)qi * k + j];
+                    out_doc[(int64_t)(q0 + qi) * k + j] = r.doc;
+                    out_score[(int64_t)(q0 + qi) * k + j] = (float)r.score;
+                    if (r.doc >= 0) ++cnt;
+                }
+                out_count[q0 + qi] = S > 1 ? pin_cnt(b)[qi] : cnt;
+                if (pin_flag(b)[qi] != 0) redo.push_back(q0 + qi);
+            }
+            g->b_passes += 1;
+            g->b_queries += nq;
+        }
+        return ANRAG_OK;
+    };
+    rc = run();
+    if (rc)  // nothing may still run on a shard's stream, or read the pinned staging, when the next call uses them again
+        for (int32_t i = 0; i < S; ++i) {
+            DeviceGuard guard(g->device[i]);
+            (void)hipStreamSynchronize(g->shard[i]->primary);
+        }
+    return rc;
+}
+
 // cold routes: the lists the shards returned, shard after shard -> the first k by (score desc), stably
 template <typename S>
 void merge_host(const std::vector<int64_t> &doc, const std::vector<S> &score, int32_t k, int64_t *out_doc, S *out_score,
@@ -434,6 +700,8 @@ int anrag_shard_group_create(const int32_t *devices, int32_t n_shards, anrag_sha
         set_error("out of host memory");
         return ANRAG_ERR_NOMEM;
     }
+    if (const char *e = getenv("ANRAG_GROUP_BATCHED"))  // "0": query lists stay on the hot route (A/B measurements)
+        g->batched_on = !(e[0] == '0' && e[1] == 0);
     auto build = [&]() -> int {
         for (int32_t i = 0; i < n_shards; ++i) {
             g->device[i] = devices[i];
@@ -452,11 +720,14 @@ int anrag_shard_group_create(const int32_t *devices, int32_t n_shards, anrag_sha
             g->d_slab[i] = cv.take<anrag_candidate>(kSlabRecords);
             g->d_allow_a[i] = cv.take<uint32_t>(2048);
             g->d_allow_b[i] = cv.take<uint32_t>(2048);
-            if (i > 0)  // the home shard's records are ordered by its own fusion stream
+            if (i > 0) {  // the home shard's records are ordered by its own streams
                 for (hipEvent_t &e : g->ev_cand[i]) ANRAG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                for (hipEvent_t &e : g->ev_pass[i]) ANRAG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            }
         }
         DeviceGuard guard(g->device[0]);
         for (hipEvent_t &e : g->ev_tail) ANRAG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        for (hipEvent_t &e : g->ev_merged) ANRAG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         ANRAG_HIP(counted_host_malloc(reinterpret_cast<void **>(&g->h_pin), kPinBytes, hipHostMallocDefault));
         g->in_place[0] = true;
         for (int32_t i = 1; i < n_shards; ++i) {
@@ -474,6 +745,10 @@ int anrag_shard_group_create(const int32_t *devices, int32_t n_shards, anrag_sha
             if (!g->in_place[i]) {
                 ANRAG_HIP(counted_malloc(&g->d_stage[i], (size_t)kSlabRecords * sizeof(anrag_candidate)));
                 g->own_bytes += kSlabRecords * (int64_t)sizeof(anrag_candidate);
+                if (g->batched_on) {
+                    ANRAG_HIP(counted_malloc(&g->d_bstage[i], kBatchedBlocks * kStageBlock));
+                    g->own_bytes += (int64_t)(kBatchedBlocks * kStageBlock);
+                }
             }
         }
         return ANRAG_OK;
@@ -502,12 +777,16 @@ int anrag_shard_group_dense_load(anrag_shard_group *g, const float *embeddings, 
     int rc;
     if ((rc = drain(g))) return rc;
     g->has_dense = false;
-    if (dim != g->dim) {  // the single query's pinned staging follows the dimension
+    if (dim != g->dim) {  // the pinned staging of the single query and of the batched route's chunks follows the dimension
         DeviceGuard guard(g->device[0]);
         if (g->h_query) (void)counted_host_free(g->h_query);
-        g->h_query = nullptr;
+        if (g->h_bq) (void)counted_host_free(g->h_bq);
+        g->h_query = g->h_bq = nullptr;
         g->dim = 0;
         ANRAG_HIP(counted_host_malloc(reinterpret_cast<void **>(&g->h_query), (size_t)dim * sizeof(float), hipHostMallocDefault));
+        if (g->batched_on)
+            ANRAG_HIP(counted_host_malloc(reinterpret_cast<void **>(&g->h_bq),
+                                          (size_t)kBatchedBlocks * kBatchedQueries * dim * sizeof(float), hipHostMallocDefault));
         g->dim = dim;
     }
     shard_bounds(n_rows, g->n, g->dense_lo);
@@ -655,6 +934,34 @@ int anrag_shard_group_dense_search(anrag_shard_group *g, const float *queries, i
         }
         return ANRAG_OK;
     }
+    bool batched = g->batched_on;  // the single index's own gate, on every shard
+    for (int32_t i = 0; i < g->n; ++i) batched = batched && batched_path_applies(g->shard[i], n_queries, k);
+    if (batched) {
+        ANRAG_REQUIRE(n_queries <= (1 << 20), "n_queries %d out of range", n_queries);
+        std::vector<int32_t> redo;
+        if (int rc = run_batched(g, queries, n_queries, k, allow_source, n_sources, out_doc, out_score, out_count, redo)) return rc;
+        if (redo.empty()) return ANRAG_OK;
+        // a survivor list overflowed on some shard (batched_select_kernel): the batch = 1 scans answer these queries, on
+        // every shard, as anrag_dense_search redoes them on one index
+        std::vector<float> rq(redo.size() * (size_t)g->dim);
+        for (size_t j = 0; j < redo.size(); ++j)
+            memcpy(rq.data() + j * g->dim, queries + (int64_t)redo[j] * g->dim, (size_t)g->dim * sizeof(float));
+        const HotCall c{kGroupDense, rq.data(), nullptr, nullptr, (int32_t)redo.size(), k, 0, 0, 0, 0,
+                        allow_source, n_sources, nullptr, 0};
+        std::vector<anrag_candidate> h;
+        std::vector<int32_t> cnt;
+        if (int rc = run_hot(g, c, h, cnt)) return rc;
+        for (size_t j = 0; j < redo.size(); ++j) {
+            const int64_t q = redo[j];
+            for (int32_t i = 0; i < k; ++i) {
+                out_doc[q * k + i] = h[j * k + i].doc;
+                out_score[q * k + i] = (float)h[j * k + i].score;
+            }
+            out_count[q] = cnt[j];
+        }
+        g->b_redone += (int64_t)redo.size();
+        return ANRAG_OK;
+    }
     const HotCall c{kGroupDense, queries, nullptr, nullptr, n_queries, k, 0, 0, 0, 0, allow_source, n_sources, nullptr, 0};
     std::vector<anrag_candidate> h;
     std::vector<int32_t> cnt;
@@ -735,6 +1042,21 @@ int anrag_shard_group_set_dense_prefilter(anrag_shard_group *g, int32_t mode) {
     ANRAG_GROUP_ENTER(g);
     for (int32_t i = 0; i < g->n; ++i)
         if (int rc = anrag_set_dense_prefilter(g->shard[i], mode)) return rc;
+    return ANRAG_OK;
+}
+
+int anrag_shard_group_set_batched_precision(anrag_shard_group *g, int32_t mode) {
+    ANRAG_GROUP_ENTER(g);
+    for (int32_t i = 0; i < g->n; ++i)
+        if (int rc = anrag_set_batched_precision(g->shard[i], mode)) return rc;
+    return ANRAG_OK;
+}
+
+int anrag_shard_group_batched_stats(anrag_shard_group *g, int64_t *passes, int64_t *queries, int64_t *redone) {
+    ANRAG_GROUP_ENTER(g);
+    if (passes) *passes = g->b_passes;
+    if (queries) *queries = g->b_queries;
+    if (redone) *redone = g->b_redone;
     return ANRAG_OK;
 }
 

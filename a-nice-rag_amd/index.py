@@ -149,7 +149,10 @@ def group_bounds(n: int, n_shards: int) -> list:
 class ShardGroup:
     """Owns an `anrag_shard_group*`: ONE corpus over several GPUs (or several shards of one GPU) in one process, with
     `Index`'s method names and return shapes for what a group serves -- every answer equals the single index's, ids,
-    counts and score bits.  Ranked lists of queries (full ranking) go through `rank_batch_group`.  `dense_scores`,
+    counts and score bits.  `dense_search` with 16 or more queries takes the matrix-core pass (K2) on every shard where
+    the single index takes it (every shard >= 65,536 rows, dim % 32 == 0, k <= 64) and merges the shards' lists on the
+    home device; `set_batched_precision` / `batched_stats` belong to that route.  Ranked lists of queries (full ranking)
+    go through `rank_batch_group`.  `dense_scores`,
     `bm25_scores` and `rank_batch` itself (it takes `Index` legs: a group has no `handle`) raise `AnragError` with code
     `ERR_UNSUPPORTED`."""
 
@@ -211,6 +214,17 @@ class ShardGroup:
 
     def set_dense_prefilter(self, mode: int = -1) -> None:
         nat.check(self._lib.anrag_shard_group_set_dense_prefilter(self.group, int(mode)))
+
+    def set_batched_precision(self, mode: str = "f32") -> None:
+        """`Index.set_batched_precision` on every shard: "f32" (default) or "bf16x3"."""
+        nat.check(self._lib.anrag_shard_group_set_batched_precision(self.group, {"f32": 0, "bf16x3": 1}[mode]))
+
+    def batched_stats(self) -> dict:
+        """The batched dense route so far: `passes` (chunks of up to 256 queries), `queries` it answered, `redone` (those
+        of them a shard flagged and the batch = 1 route answered)."""
+        p, q, r = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        nat.check(self._lib.anrag_shard_group_batched_stats(self.group, C.byref(p), C.byref(q), C.byref(r)))
+        return dict(passes=p.value, queries=q.value, redone=r.value)
 
     def dense_load(self, embeddings, source_id=None, doc_id=None, doc_id_base: int = 0) -> None:
         """Host operands only (a numpy matrix): the group cuts it into row blocks, one per shard."""

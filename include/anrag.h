@@ -503,7 +503,15 @@ int anrag_debug_prefilter_bounds(anrag_index *idx, const float *queries, int32_t
  * Ranked route (lists of queries, full ranking: anrag_shard_group_rank_batch below): every shard runs the score tiles and
  * the per-query sort of anrag_rank_batch over its own rows; the home device merges the shards' sorted lists stably in
  * shard order and runs the single index's fusion and emit.
- * Not served: anrag_rank_batch itself and the K2 batched pass (a rank leg takes an anrag_index), the ranking route of
+ * Batched dense route (anrag_shard_group_dense_search with a list of queries, where the single index's own gate holds
+ * on EVERY shard: 16 or more queries, k <= ANRAG_FUSED_K_MAX, dim % 32 == 0, 65,536 rows or more per shard): per chunk
+ * of up to 256 queries every shard runs the K2 pass of anrag_dense_search on its primary stream into a result block of
+ * its call pool and records an event; shard 0's primary stream waits for the events and runs ONE merge kernel (the same
+ * shard-order rule, ranks by counting), then copies the chunk out.  One host wait per chunk, the next chunk's passes are
+ * enqueued before it; a query whose survivor list overflowed on a shard is redone by the hot route above, as the single
+ * index redoes it with its batch = 1 scan.  ANRAG_GROUP_BATCHED=0 at anrag_shard_group_create keeps such calls on the hot
+ * route (measurements).
+ * Not served: anrag_rank_batch itself (a rank leg takes an anrag_index), the ranking route of
  * anrag_hybrid_search_batch, the *_device entries, the score dumps: there is no group entry for them; a binding
  * reports ANRAG_ERR_UNSUPPORTED (a-nice-rag_amd/index.py).
  * A group is serialised by its own mutex for the whole call. */
@@ -539,6 +547,10 @@ int anrag_shard_group_bm25_search(anrag_shard_group *g, const int32_t *term_ids,
                                   const uint8_t *allow_source, int32_t n_sources, int64_t *out_doc, double *out_score,
                                   int32_t *out_count);
 int anrag_shard_group_set_dense_prefilter(anrag_shard_group *g, int32_t mode); /* forwards to every shard */
+int anrag_shard_group_set_batched_precision(anrag_shard_group *g, int32_t mode); /* anrag_set_batched_precision, likewise */
+/* The batched dense route so far (each nullable): chunks of up to 256 queries run, queries it answered (the redone ones
+ * included), queries redone by the hot route because a shard flagged them. */
+int anrag_shard_group_batched_stats(anrag_shard_group *g, int64_t *passes, int64_t *queries, int64_t *redone);
 int anrag_shard_group_sync(anrag_shard_group *g);
 /* dense_row_lo / bm25_doc_lo (each nullable): n_shards + 1 block bounds (all 0 before the load); hbm_bytes: the shards'
  * and the group's own. */
