@@ -105,6 +105,7 @@ _SIGNATURES = {
     "anrag_debug_alloc_calls": [C.POINTER(_i64)],
     "anrag_debug_prefilter_read": [_p, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i32), _p, _p],
     "anrag_debug_prefilter_bounds": [_p, _p, _i32, _i32, _p, _i32, C.c_uint32, _p, _p],
+    "anrag_debug_dense_lists": [_p, _p, _i32, _i32, _p, _i32, C.c_uint32, C.c_uint32, C.POINTER(_i32), _p, _p],
     "anrag_rank_batch": [_p, _i32, _i32, _i32, _f64, _i32, _i64, _p, _p, _p, _p, _p],
     "anrag_rank_caps": [C.POINTER(_i32), C.POINTER(_i32)],
     "anrag_shard_group_create": [_p, _i32, C.POINTER(_p)],

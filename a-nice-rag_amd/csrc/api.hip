@@ -1604,6 +1604,66 @@ int anrag_debug_prefilter_bounds(anrag_index *idx, const float *queries, int32_t
     return ANRAG_OK;
 }
 
+int anrag_debug_dense_lists(anrag_index *idx, const float *queries, int32_t n_queries, int32_t k,
+                            const uint8_t *allow_source, int32_t n_sources, uint32_t score_sentinel, uint32_t row_sentinel,
+                            int32_t *out_n_lists, float *out_scores, uint32_t *out_rows) {
+    ANRAG_ENTER(idx);
+    ANRAG_REQUIRE(idx->d_emb != nullptr, "dense lists before anrag_dense_load");
+    ANRAG_REQUIRE(out_n_lists != nullptr, "out_n_lists is NULL");
+    const int32_t n_lists = dense_scan_lists(idx);
+    *out_n_lists = n_lists;
+    if (!out_scores && !out_rows) return ANRAG_OK;  // the size question alone
+    ANRAG_REQUIRE(queries && out_scores && out_rows, "NULL operand");
+    ANRAG_REQUIRE(n_queries >= 1 && n_queries <= kScanGroupMax, "a scan launch takes 1..%d queries", kScanGroupMax);
+    ANRAG_REQUIRE(k >= 1 && k <= ANRAG_FUSED_K_MAX, "1 <= k <= %d", ANRAG_FUSED_K_MAX);
+    ANRAG_REQUIRE(!(allow_source && !idx->d_dense_src), "a source filter needs source ids (anrag_dense_load)");
+    ANRAG_REQUIRE((score_sentinel & 0x7F800000u) == 0x7F800000u && (score_sentinel & 0x007FFFFFu) != 0 &&
+                      score_sentinel != 0x7FC00000u,
+                  "the score sentinel must be a NaN pattern other than 0x7FC00000");
+    ANRAG_REQUIRE(row_sentinel != kNoRow && (int64_t)row_sentinel >= idx->n_rows,
+                  "the row sentinel must be neither a row of the corpus nor the empty slot's 0xFFFFFFFF");
+    int rc = sync_all(idx);  // list sets 0 .. n_queries - 1 and the staging buffers are free behind this
+    if (rc) return rc;
+    hipStream_t st = idx->primary;
+    const bool pf_stats = idx->pf_on && idx->d_pf_survivors;
+    unsigned long long survivors = 0;
+    if (pf_stats) ANRAG_HIP(hipMemcpy(&survivors, idx->d_pf_survivors, sizeof(survivors), hipMemcpyDeviceToHost));
+    const uint32_t *d_allow = nullptr;
+    if ((rc = stage_allow(idx, st, allow_source, n_sources, idx->d_allow_a, reinterpret_cast<uint32_t *>(idx->h_pinned),
+                          &d_allow)))
+        return rc;
+    ANRAG_HIP(hipMemcpyAsync(idx->d_query, queries, (size_t)n_queries * idx->dim * sizeof(float), hipMemcpyHostToDevice, st));
+    int sets[kScanGroupMax];
+    const float *qs[kScanGroupMax];
+    for (int i = 0; i < n_queries; ++i) {
+        sets[i] = i;
+        qs[i] = idx->d_query + (int64_t)i * idx->dim;
+    }
+    const size_t set_len = (size_t)kMaxScanLists * kListLen;
+    ANRAG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(idx->d_blk_score_f32), (int)score_sentinel,
+                                (size_t)n_queries * set_len, st));
+    ANRAG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(idx->d_blk_row_a), (int)row_sentinel,
+                                (size_t)n_queries * set_len, st));
+    // a diagnostic scan is not a query answered: no profile span, no prefilter statistics
+    const bool profiling = idx->profiling;
+    const int64_t counted = idx->pf_queries;
+    idx->profiling = false;
+    rc = launch_dense_scan_group(idx, st, qs, n_queries, k, d_allow, nullptr, sets, 0, nullptr);
+    idx->profiling = profiling;
+    idx->pf_queries = counted;
+    if (rc) return rc;
+    ANRAG_HIP(hipStreamSynchronize(st));
+    if (pf_stats) ANRAG_HIP(hipMemcpy(idx->d_pf_survivors, &survivors, sizeof(survivors), hipMemcpyHostToDevice));
+    const size_t out_len = (size_t)n_lists * kListLen;
+    for (int i = 0; i < n_queries; ++i) {
+        ANRAG_HIP(hipMemcpy(out_scores + i * out_len, idx->d_blk_score_f32 + i * set_len, out_len * sizeof(float),
+                            hipMemcpyDeviceToHost));
+        ANRAG_HIP(hipMemcpy(out_rows + i * out_len, idx->d_blk_row_a + i * set_len, out_len * sizeof(uint32_t),
+                            hipMemcpyDeviceToHost));
+    }
+    return ANRAG_OK;
+}
+
 int anrag_index_info(anrag_index *idx, int64_t *dense_rows, int32_t *dense_dim, int64_t *bm25_docs,
                      int64_t *bm25_postings, int64_t *hbm_bytes) {
     ANRAG_ENTER(idx);

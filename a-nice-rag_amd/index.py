@@ -516,6 +516,26 @@ class Index:
                                                          self.PREFILTER_SENTINEL, hi.ctypes.data, thr.ctypes.data))
         return hi, thr
 
+    LIST_ROW_SENTINEL = 0xFFFFFFFE  # never a row (a shard holds at most 2^32 - 2), nor the empty slot's 0xFFFFFFFF
+
+    def debug_dense_lists(self, queries, k: int, allow_source=None):
+        """The per-wave lists a scan group of 1..16 queries leaves for the merge (`anrag_debug_dense_lists`)
+        -> (scores [nq, n_lists, 64] float32, rows [nq, n_lists, 64] uint32); a slot no kernel wrote holds
+        PREFILTER_SENTINEL's bits and LIST_ROW_SENTINEL, an empty slot (-inf, 0xFFFFFFFF)."""
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q[None, :]
+        assert q.shape[1] == self.dim, f"query dim {q.shape[1]} != index dim {self.dim}"
+        allow, ns = _allow_bytes(allow_source)
+        n_lists = C.c_int32(0)
+        nat.check(self._lib.anrag_debug_dense_lists(self.handle, None, 0, 0, None, 0, 0, 0, C.byref(n_lists), None, None))
+        scores = np.empty((q.shape[0], n_lists.value, 64), np.float32)
+        rows = np.empty((q.shape[0], n_lists.value, 64), np.uint32)
+        nat.check(self._lib.anrag_debug_dense_lists(self.handle, q.ctypes.data, q.shape[0], int(k), nat.ptr(allow), ns,
+                                                    self.PREFILTER_SENTINEL, self.LIST_ROW_SENTINEL, C.byref(n_lists),
+                                                    scores.ctypes.data, rows.ctypes.data))
+        return scores, rows
+
     def dense_scores(self, query) -> np.ndarray:
         q = _f32(query).reshape(-1)
         assert q.size == self.dim

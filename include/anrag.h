@@ -479,6 +479,21 @@ int anrag_debug_prefilter_read(anrag_index *idx, int32_t *out_form, int64_t *out
 int anrag_debug_prefilter_bounds(anrag_index *idx, const float *queries, int32_t n_queries, int32_t k,
                                  const uint8_t *allow_source, int32_t n_sources, uint32_t sentinel, float *out_hi,
                                  float *out_threshold);
+/* The per-wave lists of the dense top-k seen from outside, for tests of the lists and of their merges
+ * (tests/test_gpu_dense_lists.py).  Runs the list-producing half of a scan group of 1..16 queries exactly as the product
+ * runs it (list sets 0 .. n_queries - 1, the primary stream, no deferred merge riding along): the fp32 scan with the
+ * prefilter off, shadow scan + threshold + rescore with it on -- and no merge.  The sets' score and row blocks are first
+ * filled with score_sentinel (the bits of a NaN other than 0x7FC00000) and row_sentinel (neither a row of the corpus nor
+ * 0xFFFFFFFF, the row of an empty slot), so that a slot no kernel wrote shows.  Waits for the index's streams,
+ * allocates nothing, and moves no statistic (prefilter counters, profile spans).
+ * out_n_lists: lists per query (one per scan wave; a function of the corpus shape alone).  With out_scores and out_rows
+ * both NULL only that is returned and nothing runs.  queries host [n_queries][dim]; allow_source as for
+ * anrag_dense_search; out_scores host [n_queries][n_lists][64] fp32 and out_rows host [n_queries][n_lists][64]: each
+ * list sorted by (score descending, row ascending), empty slots (-inf, 0xFFFFFFFF) last; only slots [0, k) are
+ * specified when k < 64. */
+int anrag_debug_dense_lists(anrag_index *idx, const float *queries, int32_t n_queries, int32_t k,
+                            const uint8_t *allow_source, int32_t n_sources, uint32_t score_sentinel, uint32_t row_sentinel,
+                            int32_t *out_n_lists, float *out_scores, uint32_t *out_rows);
 
 /* ------------------------------------------------------------------ shard group
  * ONE corpus over several anrag_index objects in ONE process (the reference is one process: one RAGSystem for all
