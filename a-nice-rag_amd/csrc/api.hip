@@ -140,8 +140,8 @@ static void dev_free(anrag_index *idx, T *&p, int64_t count) {
 static int ensure_common_workspace(anrag_index *idx) {
     int rc;
     if (!idx->d_allow_a) {
-        if ((rc = dev_alloc(idx, &idx->d_allow_a, 2048))) return rc;
-        if ((rc = dev_alloc(idx, &idx->d_allow_b, 2048))) return rc;
+        if ((rc = dev_alloc(idx, &idx->d_allow_a, kAllowWords))) return rc;
+        if ((rc = dev_alloc(idx, &idx->d_allow_b, kAllowWords))) return rc;
         if ((rc = dev_alloc(idx, &idx->d_terms, 4096))) return rc;
     }
     if (!idx->d_cand_a) {
@@ -166,42 +166,46 @@ static int ensure_query_buffer(anrag_index *idx, int64_t floats) {
     return ANRAG_OK;
 }
 
-// bytes-per-source allow list (host) -> 2048-word bitmap staged in HBM; NULL allow -> nullptr (no filter)
-static int stage_allow(anrag_index *idx, hipStream_t st, const uint8_t *allow, int32_t n_sources, uint32_t *d_bits,
-                       uint32_t *h_bits, const uint32_t **out) {
-    *out = nullptr;
-    if (!allow) return ANRAG_OK;
+int pack_allow_bits(const uint8_t *allow, int32_t n_sources, uint32_t *h_bits) {
     ANRAG_REQUIRE(n_sources >= 0 && n_sources <= 65536, "n_sources %d out of range [0, 65536]", n_sources);
-    memset(h_bits, 0, 2048 * sizeof(uint32_t));
+    memset(h_bits, 0, kAllowWords * sizeof(uint32_t));
     for (int32_t s = 0; s < n_sources; ++s)
         if (allow[s]) h_bits[s >> 5] |= 1u << (s & 31);
-    ANRAG_HIP(hipMemcpyAsync(d_bits, h_bits, 2048 * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    return ANRAG_OK;
+}
+
+// allow list (one byte per source, host) -> bitmap in the pinned h_bits -> d_bits, asynchronously on `st`; NULL allow ->
+// *out = nullptr (no filter)
+static int stage_allow(hipStream_t st, const uint8_t *allow, int32_t n_sources, uint32_t *h_bits, uint32_t *d_bits,
+                       const uint32_t **out) {
+    *out = nullptr;
+    if (!allow) return ANRAG_OK;
+    if (int rc = pack_allow_bits(allow, n_sources, h_bits)) return rc;
+    ANRAG_HIP(hipMemcpyAsync(d_bits, h_bits, kAllowWords * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     *out = d_bits;
     return ANRAG_OK;
 }
 
-// the merges still riding behind the lanes' last scans: launched on their own, each on its lane's stream
+// the merge still riding behind a lane's last scan, if any: launched on its own, on the lane's stream
+static int launch_pending_tail(anrag_index *idx, anrag_index::ScanLane &ln) {
+    if (!ln.pending) return ANRAG_OK;
+    ln.pending = false;
+    return launch_tail(idx, ln.st, ln.tail.set, /*dense*/ true, /*bm25*/ false, ln.tail.k, kTailCandidates, 0, 0, 0, 0,
+                       ln.tail.out, nullptr);
+}
+
 static int flush_lanes(anrag_index *idx) {
-    if (!idx->lanes_active) return ANRAG_OK;
-    for (int l = 0; l < kScanLanesMax; ++l) {
-        anrag_index::ScanLane &ln = idx->lane[l];
-        if (!ln.pending) continue;
-        ln.pending = false;
-        int rc = launch_tail(idx, ln.st, ln.tail.set, /*dense*/ true, /*bm25*/ false, ln.tail.k, kTailCandidates, 0, 0, 0, 0,
-                             ln.tail.out, nullptr);
-        if (rc) return rc;
-    }
+    if (!idx->lanes.active) return ANRAG_OK;
+    for (anrag_index::ScanLane &ln : idx->lane)
+        if (int rc = launch_pending_tail(idx, ln)) return rc;
     return ANRAG_OK;
 }
 
 int sync_all(anrag_index *idx) {
-    if (idx->lanes_active) {
+    if (idx->lanes.active) {
         int rc = flush_lanes(idx);
-        for (int l = 0; l < kScanLanesMax; ++l) {
-            ANRAG_HIP(hipStreamSynchronize(idx->lane[l].st));
-            idx->lane[l].count = 0;
-        }
-        idx->lanes_active = false;
+        for (int l = 0; l < kScanLanesMax; ++l) ANRAG_HIP(hipStreamSynchronize(idx->lane[l].st));
+        idx->lanes.reset();
         if (rc) return rc;
     }
     ANRAG_HIP(hipStreamSynchronize(idx->primary));
@@ -223,6 +227,31 @@ int settle_pipeline(anrag_index *idx) {
 // flight would only stretch each query's latency.
 constexpr int kScanLanesDefault = 4;
 constexpr int64_t kScanLanesMaxBytes = 1ll << 30;
+
+// One single query on the lanes (scan_lanes.hpp has the bookkeeping and its invariant): lane_acquire, the query's
+// launches on the lane's stream, lane_commit.  Per-query path: inline.
+static inline int lanes_activate(anrag_index *idx) {
+    if (idx->lanes.active) return ANRAG_OK;
+    if (int rc = settle_pipeline(idx)) return rc;  // the pipeline's queries own the same list sets
+    idx->lanes.activate(idx->n_lanes, (int64_t)idx->n_rows * idx->dim * 4 > kScanLanesMaxBytes);
+    return ANRAG_OK;
+}
+
+// the next query's lane and list set; backpressure is on the HOST: wait for the event behind the set's previous user
+__attribute__((always_inline)) static inline int lane_acquire(anrag_index *idx, ScanLanes::Ticket *t) {
+    if (int rc = lanes_activate(idx)) return rc;
+    *t = idx->lanes.acquire();
+    const hipEvent_t *ev = idx->lane[t->lane].ev;
+    if (t->wait_ev >= 0 && hipEventQuery(ev[t->wait_ev]) != hipSuccess) ANRAG_HIP(hipEventSynchronize(ev[t->wait_ev]));
+    return ANRAG_OK;
+}
+
+__attribute__((always_inline)) static inline int lane_commit(anrag_index *idx, int lane) {
+    const int ev = idx->lanes.commit(lane);
+    if (ev >= 0) ANRAG_HIP(hipEventRecord(idx->lane[lane].ev[ev], idx->lane[lane].st));
+    idx->hyb_outstanding = true;
+    return ANRAG_OK;
+}
 
 // The dense prefilter's mode applied to the loaded corpus (anrag_set_dense_prefilter): auto builds the int8 form past
 // kScanLanesMaxBytes of fp32 corpus and stays on K1 when it cannot allocate; modes 1 (fp16) and 2 (int8) report
@@ -406,7 +435,7 @@ int anrag_index_wait_stream(anrag_index *idx, void *stream) {
 int anrag_index_signal_stream(anrag_index *idx, void *stream) {
     ANRAG_ENTER(idx);
     if (!idx->ev_order) ANRAG_HIP(hipEventCreateWithFlags(&idx->ev_order, hipEventDisableTiming));
-    if (idx->lanes_active) {  // single dense queries: launch the merges still pending, then the lanes' streams count too
+    if (idx->lanes.active) {  // single dense queries: launch the merges still pending, then the lanes' streams count too
         if (int rc = flush_lanes(idx)) return rc;
         for (int l = 0; l < kScanLanesMax; ++l) {
             ANRAG_HIP(hipEventRecord(idx->ev_order, idx->lane[l].st));
@@ -465,41 +494,33 @@ struct GroupQuery {
 static int hybrid_enqueue_group(anrag_index *idx, TailMode tail, const GroupQuery *q, int32_t n, int32_t k,
                                 double w_dense, double w_bm25, double wrrf_k, int32_t top_n,
                                 const uint32_t *d_allow_dense, const uint32_t *d_allow_bm25);
-// One dense-only query per call on the index's own streams: lane = query number mod n_lanes.  A lane owns
-// kPipeSlots / n_lanes list sets; the merge of its previous query rides in the scan launch of this one (DeferredTail),
-// so a lane's stream carries scans only -- no marker, no second stream -- and the lanes overlap.  Backpressure: an event
-// every quarter of a lane's sets; before a set is reused the call waits (on the HOST) for the launch that carried the
-// merge of its previous user.  The last merges are launched by whatever drains the index (sync_all).
+// Which legs query `q` has.  A query vector asks for the dense leg -- one scan launch serves a whole group, all or none,
+// so the group's `first` query decides it (a single query is its own first); term ids ask for the BM25 leg.  No term ids:
+// BM25 is skipped as the reference skips it (search_engine.py:216-217) -- except for a BM25-only candidate query, which
+// then ranks all-zero scores like anrag_bm25_search does.
+static inline int query_legs(const anrag_index *idx, TailMode tail, const GroupQuery &first, const GroupQuery &q, double w_dense,
+                      double w_bm25, bool *use_dense, bool *use_bm25) {
+    *use_dense = idx->d_emb != nullptr && first.d_query != nullptr && (tail != kTailFuse || w_dense > 0.0);
+    *use_bm25 = idx->d_post_doc != nullptr && (tail != kTailFuse || w_bm25 > 0.0) &&
+                (q.n_terms > 0 || (!*use_dense && tail != kTailFuse));
+    ANRAG_REQUIRE(*use_dense || *use_bm25, "hybrid search with neither a dense nor a BM25 leg");
+    return ANRAG_OK;
+}
+
+// One dense-only query per call on the index's own streams takes the next lane.  The merge of the lane's previous query
+// rides in the scan launch of this one (DeferredTail), so a lane's stream carries scans only -- no marker, no second
+// stream -- and the lanes overlap.  The last merges are launched by whatever drains the index (sync_all).
 static int dense_single_enqueue(anrag_index *idx, const float *d_query, int32_t k, const uint32_t *d_allow,
                                 anrag_candidate *d_out) {
     int rc;
-    if (!idx->lanes_active) {
-        if ((rc = settle_pipeline(idx))) return rc;  // the pipeline's queries own the same list sets
-        idx->lanes_active = true;
-        idx->lane_rr = 0;
-        idx->lanes_in_use = (int64_t)idx->n_rows * idx->dim * 4 > kScanLanesMaxBytes ? 1 : idx->n_lanes;
-    }
-    const int L = idx->lanes_in_use;
-    const int l = (int)(idx->lane_rr++ % (uint64_t)L);
-    anrag_index::ScanLane &ln = idx->lane[l];
-    const int per_lane = kPipeSlots / L, every = per_lane / 4;
-    const uint64_t ls = ln.count;
-    const int set = l * per_lane + (int)(ls % (uint64_t)per_lane);
-    if (ls >= (uint64_t)per_lane) {
-        // the set's previous user is lane query ls - per_lane; its merge rode in launch ls - per_lane + 1; event m
-        // was recorded behind launch (m + 1) * every - 1
-        const int64_t m = ((int64_t)ls - per_lane + 2 + every - 1) / every - 1;
-        hipEvent_t ev = ln.ev[m % 4];
-        if (hipEventQuery(ev) != hipSuccess) ANRAG_HIP(hipEventSynchronize(ev));
-    }
-    if ((rc = launch_dense_scan_group(idx, ln.st, &d_query, 1, k, d_allow, nullptr, &set, 0, ln.pending ? &ln.tail : nullptr)))
+    ScanLanes::Ticket t;
+    if ((rc = lane_acquire(idx, &t))) return rc;
+    anrag_index::ScanLane &ln = idx->lane[t.lane];
+    if ((rc = launch_dense_scan_group(idx, ln.st, &d_query, 1, k, d_allow, nullptr, &t.set, 0, ln.pending ? &ln.tail : nullptr)))
         return rc;
     ln.pending = true;
-    ln.tail = PendingTail{set, k, d_out};
-    ln.count = ls + 1;
-    if (ln.count % (uint64_t)every == 0) ANRAG_HIP(hipEventRecord(ln.ev[(ln.count / every - 1) % 4], ln.st));
-    idx->hyb_outstanding = true;
-    return ANRAG_OK;
+    ln.tail = PendingTail{t.set, k, d_out};
+    return lane_commit(idx, t.lane);
 }
 
 constexpr int kRankRouteMin = 16;  // queries from which anrag_hybrid_search_batch takes the ranking route
@@ -545,7 +566,7 @@ int anrag_dense_search_f64(anrag_index *idx, const double *query, int32_t k, con
     if ((rc = settle_pipeline(idx))) return rc;
     const uint32_t *d_allow = nullptr;
     uint32_t *h_bits = reinterpret_cast<uint32_t *>(idx->h_pinned);
-    if ((rc = stage_allow(idx, st, allow_source, n_sources, idx->d_allow_a, h_bits, &d_allow))) return rc;
+    if ((rc = stage_allow(st, allow_source, n_sources, h_bits, idx->d_allow_a, &d_allow))) return rc;
     return dense_search_f64(idx, st, query, k, d_allow, out_doc, out_score, out_count);
 }
 
@@ -610,14 +631,8 @@ static int dense_search_batched_host(anrag_index *idx, hipStream_t st, const flo
                     }
                 }
             }
-            int32_t cnt = 0;
-            for (int32_t i = 0; i < k; ++i) {
-                const anrag_candidate &c = h[(size_t)qi * k + i];
-                out_doc[(int64_t)(q0 + qi) * k + i] = c.doc;
-                out_score[(int64_t)(q0 + qi) * k + i] = (float)c.score;
-                if (c.doc >= 0) ++cnt;
-            }
-            out_count[q0 + qi] = cnt;
+            const int64_t at = (int64_t)(q0 + qi) * k;
+            unpack_records(h.data() + (size_t)qi * k, k, out_doc + at, out_score + at, out_count + q0 + qi);
         }
     }
     return rc;
@@ -676,14 +691,14 @@ int anrag_dense_search(anrag_index *idx, const float *queries, int32_t n_queries
     if ((rc = settle_pipeline(idx))) return rc;  // list set 0 and the staging buffers below belong to the pipeline too
     const uint32_t *d_allow = nullptr;
     uint32_t *h_bits = reinterpret_cast<uint32_t *>(idx->h_pinned);
-    if ((rc = stage_allow(idx, st, allow_source, n_sources, idx->d_allow_a, h_bits, &d_allow))) return rc;
+    if ((rc = stage_allow(st, allow_source, n_sources, h_bits, idx->d_allow_a, &d_allow))) return rc;
     ANRAG_REQUIRE(!(allow_source && !idx->d_dense_src), "a source filter needs source ids (anrag_dense_load)");
     if (k > ANRAG_FUSED_K_MAX) {
         return dense_search_large_k(idx, st, queries, n_queries, k, d_allow, out_doc, out_score, out_count);
     }
     if (batched_path_applies(idx, n_queries, k))
         return dense_search_batched_host(idx, st, queries, n_queries, k, d_allow, out_doc, out_score, out_count);
-    anrag_candidate *h_cand = reinterpret_cast<anrag_candidate *>(static_cast<char *>(idx->h_pinned) + 8192);
+    anrag_candidate *h_cand = reinterpret_cast<anrag_candidate *>(h_bits + kAllowWords);
     const int32_t chunk = (int32_t)std::min<int64_t>(64, idx->cand_cap / k);
     for (int32_t q0 = 0; q0 < n_queries; q0 += chunk) {
         const int32_t nq = std::min(chunk, n_queries - q0);
@@ -697,14 +712,8 @@ int anrag_dense_search(anrag_index *idx, const float *queries, int32_t n_queries
                                  hipMemcpyDeviceToHost, st));
         ANRAG_HIP(hipStreamSynchronize(st));
         for (int32_t qi = 0; qi < nq; ++qi) {
-            int32_t cnt = 0;
-            for (int32_t i = 0; i < k; ++i) {
-                const anrag_candidate &c = h_cand[(int64_t)qi * k + i];
-                out_doc[(int64_t)(q0 + qi) * k + i] = c.doc;
-                out_score[(int64_t)(q0 + qi) * k + i] = (float)c.score;
-                if (c.doc >= 0) ++cnt;
-            }
-            out_count[q0 + qi] = cnt;
+            const int64_t at = (int64_t)(q0 + qi) * k;
+            unpack_records(h_cand + (int64_t)qi * k, k, out_doc + at, out_score + at, out_count + q0 + qi);
         }
     }
     return ANRAG_OK;
@@ -783,22 +792,16 @@ int anrag_bm25_search(anrag_index *idx, const int32_t *term_ids, int32_t n_terms
     int rc;
     if ((rc = settle_pipeline(idx))) return rc;  // list set 0 and the staging buffers below belong to the pipeline too
     const uint32_t *d_allow = nullptr;
-    uint32_t *h_bits = reinterpret_cast<uint32_t *>(static_cast<char *>(idx->h_pinned) + 8192);
-    if ((rc = stage_allow(idx, st, allow_source, n_sources, idx->d_allow_b, h_bits, &d_allow))) return rc;
+    uint32_t *h_bits = reinterpret_cast<uint32_t *>(idx->h_pinned) + kAllowWords;  // (the dense bitmap's place first)
+    if ((rc = stage_allow(st, allow_source, n_sources, h_bits, idx->d_allow_b, &d_allow))) return rc;
     if ((rc = stage_terms(idx, st, term_ids, n_terms))) return rc;
     if (k > ANRAG_FUSED_K_MAX)
         return bm25_search_large_k(idx, st, idx->d_terms, n_terms, k, d_allow, out_doc, out_score, out_count);
     if ((rc = launch_bm25(idx, st, idx->d_terms, n_terms, k, d_allow, idx->d_cand_out, nullptr))) return rc;
-    anrag_candidate *h_cand = reinterpret_cast<anrag_candidate *>(static_cast<char *>(idx->h_pinned) + 16384);
+    anrag_candidate *h_cand = reinterpret_cast<anrag_candidate *>(h_bits + kAllowWords);
     ANRAG_HIP(hipMemcpyAsync(h_cand, idx->d_cand_out, (size_t)k * sizeof(anrag_candidate), hipMemcpyDeviceToHost, st));
     ANRAG_HIP(hipStreamSynchronize(st));
-    int32_t cnt = 0;
-    for (int32_t i = 0; i < k; ++i) {
-        out_doc[i] = h_cand[i].doc;
-        out_score[i] = h_cand[i].score;
-        if (h_cand[i].doc >= 0) ++cnt;
-    }
-    *out_count = cnt;
+    unpack_records(h_cand, k, out_doc, out_score, out_count);
     return ANRAG_OK;
 }
 
@@ -920,18 +923,12 @@ static int hybrid_enqueue_group(anrag_index *idx, TailMode tail, const GroupQuer
                                 double w_dense, double w_bm25, double wrrf_k, int32_t top_n,
                                 const uint32_t *d_allow_dense, const uint32_t *d_allow_bm25) {
     ANRAG_REQUIRE(n >= 1 && n <= kScanGroupMax && n <= kPipeSlots, "group of %d queries", n);
-    if (idx->lanes_active)  // single dense queries were using the list sets: drain them first (a rare change of mode)
+    if (idx->lanes.active)  // single dense queries were using the list sets: drain them first (a rare change of mode)
         if (int rc0 = sync_all(idx)) return rc0;
-    // legs: a query vector asks for the dense leg (one scan launch serves the whole group: all or none); term ids
-    // ask for the BM25 leg.  No term ids: BM25 is skipped as the reference skips it (search_engine.py:216-217) --
-    // except for a BM25-only candidate query, which then ranks all-zero scores like anrag_bm25_search does.
-    const bool use_dense = idx->d_emb != nullptr && q[0].d_query != nullptr && (tail != kTailFuse || w_dense > 0.0);
-    bool use_bm25[kScanGroupMax];
+    bool use_dense = false, use_bm25[kScanGroupMax];
     for (int i = 0; i < n; ++i) {
+        if (int rc0 = query_legs(idx, tail, q[0], q[i], w_dense, w_bm25, &use_dense, &use_bm25[i])) return rc0;
         ANRAG_REQUIRE(!use_dense || q[i].d_query != nullptr, "query %d of the group has no query vector", i);
-        use_bm25[i] = idx->d_post_doc != nullptr && (tail != kTailFuse || w_bm25 > 0.0) &&
-                      (q[i].n_terms > 0 || (!use_dense && tail != kTailFuse));
-        ANRAG_REQUIRE(use_dense || use_bm25[i], "hybrid search with neither a dense nor a BM25 leg");
     }
     hipStream_t P = idx->primary, S = idx->secondary, F = idx->fusion;
     int slot[kScanGroupMax];
@@ -1013,65 +1010,39 @@ static bool hybrid_lane_route(const anrag_index *idx) {
            (int64_t)idx->n_rows * idx->dim * 4 <= max_bytes;
 }
 
-static int lanes_activate(anrag_index *idx) {
-    if (idx->lanes_active) return ANRAG_OK;
-    if (int rc = settle_pipeline(idx)) return rc;  // the pipeline's queries own the same list sets
-    idx->lanes_active = true;
-    idx->lane_rr = 0;
-    idx->lanes_in_use = (int64_t)idx->n_rows * idx->dim * 4 > kScanLanesMaxBytes ? 1 : idx->n_lanes;
-    return ANRAG_OK;
-}
-
 // the stream the NEXT lane query of this index will be launched on (the caller holds the index's lock): operands staged on
 // it are in place when the query's kernels start, results copied on it follow the tail
 static int hybrid_lane_peek(anrag_index *idx, hipStream_t *st) {
     if (int rc = lanes_activate(idx)) return rc;
-    *st = idx->lane[idx->lane_rr % (uint64_t)idx->lanes_in_use].st;
+    *st = idx->lane[idx->lanes.peek()].st;
     return ANRAG_OK;
 }
 
 static int hybrid_lane_enqueue(anrag_index *idx, TailMode tail, const GroupQuery &q, int32_t k, double w_dense,
                                double w_bm25, double wrrf_k, int32_t top_n, const uint32_t *d_allow_dense,
                                const uint32_t *d_allow_bm25) {
-    const bool use_dense = q.d_query != nullptr && (tail != kTailFuse || w_dense > 0.0);
-    bool use_bm25 = idx->d_post_doc != nullptr && (tail != kTailFuse || w_bm25 > 0.0) &&
-                    (q.n_terms > 0 || (!use_dense && tail != kTailFuse));
-    ANRAG_REQUIRE(use_dense || use_bm25, "hybrid search with neither a dense nor a BM25 leg");
+    bool use_dense, use_bm25;
     int rc;
-    if ((rc = lanes_activate(idx))) return rc;
-    const int L = idx->lanes_in_use;
-    const int l = (int)(idx->lane_rr++ % (uint64_t)L);
-    anrag_index::ScanLane &ln = idx->lane[l];
-    const int per_lane = kPipeSlots / L, every = per_lane / 4;
-    const uint64_t ls = ln.count;
-    const int set = l * per_lane + (int)(ls % (uint64_t)per_lane);
-    if (ls >= (uint64_t)per_lane) {  // the set's previous user: as in dense_single_enqueue (its event also covers a tail
-                                     // that ran right behind its own launches)
-        const int64_t m = ((int64_t)ls - per_lane + 2 + every - 1) / every - 1;
-        hipEvent_t ev = ln.ev[m % 4];
-        if (hipEventQuery(ev) != hipSuccess) ANRAG_HIP(hipEventSynchronize(ev));
-    }
+    if ((rc = query_legs(idx, tail, q, q, w_dense, w_bm25, &use_dense, &use_bm25))) return rc;  // (a corpus is loaded)
+    ScanLanes::Ticket t;
+    if ((rc = lane_acquire(idx, &t))) return rc;
+    anrag_index::ScanLane &ln = idx->lane[t.lane];
     if (use_dense) {
-        if ((rc = launch_dense_scan_group(idx, ln.st, &q.d_query, 1, k, d_allow_dense, nullptr, &set, 0,
+        if ((rc = launch_dense_scan_group(idx, ln.st, &q.d_query, 1, k, d_allow_dense, nullptr, &t.set, 0,
                                           ln.pending ? &ln.tail : nullptr)))
             return rc;
         ln.pending = false;
-    } else if (ln.pending) {  // no scan launch to carry a dense query's merge: launch it
-        ln.pending = false;
-        if ((rc = launch_tail(idx, ln.st, ln.tail.set, true, false, ln.tail.k, kTailCandidates, 0, 0, 0, 0, ln.tail.out, nullptr)))
-            return rc;
+    } else if ((rc = launch_pending_tail(idx, ln))) {  // no scan launch to carry a dense query's merge: launch it
+        return rc;
     }
-    if (use_bm25 && (rc = launch_bm25_lists_group(idx, ln.st, &q.d_terms, &q.n_terms, 1, k, d_allow_bm25, nullptr, &set)))
+    if (use_bm25 && (rc = launch_bm25_lists_group(idx, ln.st, &q.d_terms, &q.n_terms, 1, k, d_allow_bm25, nullptr, &t.set)))
         return rc;
     anrag_candidate *out = q.d_out;
     int32_t *cnt = q.d_count;
-    if ((rc = launch_tail_group(idx, ln.st, &set, use_dense, &use_bm25, 1, k, tail, w_dense, w_bm25, wrrf_k, top_n, &out,
+    if ((rc = launch_tail_group(idx, ln.st, &t.set, use_dense, &use_bm25, 1, k, tail, w_dense, w_bm25, wrrf_k, top_n, &out,
                                 cnt ? &cnt : nullptr)))
         return rc;
-    ln.count = ls + 1;
-    if (ln.count % (uint64_t)every == 0) ANRAG_HIP(hipEventRecord(ln.ev[(ln.count / every - 1) % 4], ln.st));
-    idx->hyb_outstanding = true;
-    return ANRAG_OK;
+    return lane_commit(idx, t.lane);
 }
 
 static int hybrid_enqueue(anrag_index *idx, TailMode tail, const float *d_query, const int32_t *d_terms,
@@ -1138,8 +1109,18 @@ int anrag_hybrid_search_device(anrag_index *idx, const float *d_query, const int
 // records), and the caller holds the index lock only while it ENQUEUES: it waits for its own result outside the
 // lock, so callers on several threads (the reference shares one SearchEngine across Streamlit session threads,
 // src/app.py:17-27) overlap like back-to-back device calls do -- scans adjacent on the primary stream.
-static constexpr size_t kSlotTerms = 4096 * sizeof(int32_t), kSlotAllow = 2048 * sizeof(uint32_t),
-                        kSlotOut = 2 * ANRAG_FUSED_K_MAX * sizeof(anrag_candidate);
+// byte offsets inside one slot's block, pinned and device alike (the query is at 0):
+// query | terms | allow (dense) | allow (BM25) | result records | count
+struct HostSlotLayout {
+    size_t terms, allow_a, allow_b, out, count, bytes;
+    explicit HostSlotLayout(int32_t dim)
+        : terms(((size_t)dim * sizeof(float) + 255) / 256 * 256),
+          allow_a(terms + 4096 * sizeof(int32_t)),
+          allow_b(allow_a + kAllowWords * sizeof(uint32_t)),
+          out(allow_b + kAllowWords * sizeof(uint32_t)),
+          count(out + 2 * ANRAG_FUSED_K_MAX * sizeof(anrag_candidate)),
+          bytes(count + 256) {}
+};
 
 static void free_host_slots(anrag_index *idx) {
     if (idx->host_slots_h) (void)counted_host_free(idx->host_slots_h);
@@ -1153,40 +1134,25 @@ static void free_host_slots(anrag_index *idx) {
     idx->host_ring.sized_for = 0;
 }
 
-// (re)allocate the slots' staging for rows of `dim` floats: ONE pinned block and ONE device block, carved per slot:
-// query | terms | allow (dense) | allow (BM25) | result records | count.  Called by the ring when no slot is busy.
+// (re)allocate the slots' staging for rows of `dim` floats: ONE pinned block and ONE device block, a HostSlotLayout per
+// slot.  Called by the ring when no slot is busy.
 static int alloc_host_slots(anrag_index *idx, int32_t dim) {
     free_host_slots(idx);
-    const size_t qbytes = ((size_t)dim * sizeof(float) + 255) / 256 * 256;
-    const size_t slot_bytes = qbytes + kSlotTerms + 2 * kSlotAllow + kSlotOut + 256;
-    ANRAG_HIP(counted_host_malloc(reinterpret_cast<void **>(&idx->host_slots_h), slot_bytes * kPipeSlots, hipHostMallocDefault));
-    ANRAG_HIP(counted_malloc(reinterpret_cast<void **>(&idx->host_slots_d), slot_bytes * kPipeSlots));
+    const HostSlotLayout lay(dim);
+    ANRAG_HIP(counted_host_malloc(reinterpret_cast<void **>(&idx->host_slots_h), lay.bytes * kPipeSlots, hipHostMallocDefault));
+    ANRAG_HIP(counted_malloc(reinterpret_cast<void **>(&idx->host_slots_d), lay.bytes * kPipeSlots));
     for (int i = 0; i < kPipeSlots; ++i) {
         anrag_index::HostSlot &hs = idx->host_slot[i];
-        hs.h = idx->host_slots_h + (size_t)i * slot_bytes;
-        char *d = idx->host_slots_d + (size_t)i * slot_bytes;
+        hs.h = idx->host_slots_h + (size_t)i * lay.bytes;
+        char *d = idx->host_slots_d + (size_t)i * lay.bytes;
         hs.d_query = reinterpret_cast<float *>(d);
-        hs.d_terms = reinterpret_cast<int32_t *>(d + qbytes);
-        hs.d_allow_a = reinterpret_cast<uint32_t *>(d + qbytes + kSlotTerms);
-        hs.d_allow_b = reinterpret_cast<uint32_t *>(d + qbytes + kSlotTerms + kSlotAllow);
-        hs.d_out = reinterpret_cast<anrag_candidate *>(d + qbytes + kSlotTerms + 2 * kSlotAllow);
-        hs.d_count = reinterpret_cast<int32_t *>(d + qbytes + kSlotTerms + 2 * kSlotAllow + kSlotOut);
+        hs.d_terms = reinterpret_cast<int32_t *>(d + lay.terms);
+        hs.d_allow_a = reinterpret_cast<uint32_t *>(d + lay.allow_a);
+        hs.d_allow_b = reinterpret_cast<uint32_t *>(d + lay.allow_b);
+        hs.d_out = reinterpret_cast<anrag_candidate *>(d + lay.out);
+        hs.d_count = reinterpret_cast<int32_t *>(d + lay.count);
         ANRAG_HIP(hipEventCreateWithFlags(&hs.done, hipEventDisableTiming));
     }
-    return ANRAG_OK;
-}
-
-// allow list (one byte per source) -> bitmap in the slot's pinned block -> device, asynchronously
-static int stage_allow_slot(hipStream_t st, const uint8_t *allow, int32_t n_sources, uint32_t *h_bits, uint32_t *d_bits,
-                            const uint32_t **out) {
-    *out = nullptr;
-    if (!allow) return ANRAG_OK;
-    ANRAG_REQUIRE(n_sources >= 0 && n_sources <= 65536, "n_sources %d out of range [0, 65536]", n_sources);
-    memset(h_bits, 0, kSlotAllow);
-    for (int32_t s = 0; s < n_sources; ++s)
-        if (allow[s]) h_bits[s >> 5] |= 1u << (s & 31);
-    ANRAG_HIP(hipMemcpyAsync(d_bits, h_bits, kSlotAllow, hipMemcpyHostToDevice, st));
-    *out = d_bits;
     return ANRAG_OK;
 }
 
@@ -1208,8 +1174,6 @@ struct HybridHostQuery {
     double *out_score;
     int32_t *out_count;
     bool dense = false;
-
-    size_t qbytes() const { return ((size_t)idx->host_ring.sized_for * sizeof(float) + 255) / 256 * 256; }
 
     int prepare(std::unique_lock<std::mutex> &lock) {
         ANRAG_REQUIRE(out_id && out_score && out_count, "NULL operand");
@@ -1237,14 +1201,13 @@ struct HybridHostQuery {
             if ((r0 = hybrid_lane_peek(idx, &P))) return r0;
             S = P;
         }
-        char *h_terms = hs.h + qbytes(), *h_aa = h_terms + kSlotTerms, *h_ab = h_aa + kSlotAllow, *h_out = h_ab + kSlotAllow;
-        char *h_cnt = h_out + kSlotOut;
+        const HostSlotLayout lay(idx->host_ring.sized_for);
+        char *h_terms = hs.h + lay.terms;
         const uint32_t *d_ad = nullptr, *d_ab = nullptr;
         int r;
-        if ((r = stage_allow_slot(P, allow_dense, n_dense_sources, reinterpret_cast<uint32_t *>(h_aa), hs.d_allow_a, &d_ad)))
-            return r;
-        if ((r = stage_allow_slot(S, allow_bm25, n_bm25_sources, reinterpret_cast<uint32_t *>(h_ab), hs.d_allow_b, &d_ab)))
-            return r;
+        uint32_t *h_aa = reinterpret_cast<uint32_t *>(hs.h + lay.allow_a), *h_ab = reinterpret_cast<uint32_t *>(hs.h + lay.allow_b);
+        if ((r = stage_allow(P, allow_dense, n_dense_sources, h_aa, hs.d_allow_a, &d_ad))) return r;
+        if ((r = stage_allow(S, allow_bm25, n_bm25_sources, h_ab, hs.d_allow_b, &d_ab))) return r;
         if (dense) {
             memcpy(hs.h, query, (size_t)idx->dim * sizeof(float));
             ANRAG_HIP(hipMemcpyAsync(hs.d_query, hs.h, (size_t)idx->dim * sizeof(float), hipMemcpyHostToDevice, P));
@@ -1264,8 +1227,8 @@ struct HybridHostQuery {
             return r;
         }
         // the fused tail runs on the secondary stream: the results follow it down
-        ANRAG_HIP(hipMemcpyAsync(h_out, hs.d_out, (size_t)top_n * sizeof(anrag_candidate), hipMemcpyDeviceToHost, S));
-        ANRAG_HIP(hipMemcpyAsync(h_cnt, hs.d_count, sizeof(int32_t), hipMemcpyDeviceToHost, S));
+        ANRAG_HIP(hipMemcpyAsync(hs.h + lay.out, hs.d_out, (size_t)top_n * sizeof(anrag_candidate), hipMemcpyDeviceToHost, S));
+        ANRAG_HIP(hipMemcpyAsync(hs.h + lay.count, hs.d_count, sizeof(int32_t), hipMemcpyDeviceToHost, S));
         ANRAG_HIP(hipEventRecord(hs.done, S));
         return ANRAG_OK;
     }
@@ -1279,9 +1242,10 @@ struct HybridHostQuery {
         return ANRAG_OK;
     }
     void fetch(int s) {
-        const char *h_out = idx->host_slot[s].h + qbytes() + kSlotTerms + 2 * kSlotAllow;
-        const anrag_candidate *h_cand = reinterpret_cast<const anrag_candidate *>(h_out);
-        const int32_t cnt = std::min(*reinterpret_cast<const int32_t *>(h_out + kSlotOut), top_n);
+        const HostSlotLayout lay(idx->host_ring.sized_for);
+        const char *h = idx->host_slot[s].h;
+        const anrag_candidate *h_cand = reinterpret_cast<const anrag_candidate *>(h + lay.out);
+        const int32_t cnt = std::min(*reinterpret_cast<const int32_t *>(h + lay.count), top_n);
         for (int32_t i = 0; i < cnt; ++i) {
             out_id[i] = h_cand[i].doc;
             out_score[i] = h_cand[i].score;
@@ -1362,29 +1326,22 @@ int anrag_hybrid_search_batch(anrag_index *idx, const float *queries, const int3
     if ((rc = settle_pipeline(idx))) return rc;
     if ((rc = ensure_common_workspace(idx))) return rc;
     hipStream_t P = idx->primary;
-    char *pin = static_cast<char *>(idx->h_pinned);
+    uint32_t *pin = static_cast<uint32_t *>(idx->h_pinned);
     const uint32_t *d_ad = nullptr, *d_ab = nullptr;
-    if ((rc = stage_allow(idx, P, allow_dense, n_dense_sources, idx->d_allow_a, reinterpret_cast<uint32_t *>(pin), &d_ad)))
-        return rc;
-    if ((rc = stage_allow(idx, P, allow_bm25, n_bm25_sources, idx->d_allow_b, reinterpret_cast<uint32_t *>(pin + 8192),
-                          &d_ab)))
-        return rc;
+    if ((rc = stage_allow(P, allow_dense, n_dense_sources, pin, idx->d_allow_a, &d_ad))) return rc;
+    if ((rc = stage_allow(P, allow_bm25, n_bm25_sources, pin + kAllowWords, idx->d_allow_b, &d_ab))) return rc;
     // one call's operands and results: carved from the index's grow-only call pool, so a steady-state loop of list
     // calls allocates nothing (hipMalloc / hipFree synchronise the whole device)
-    Carver measure(nullptr);
-    auto carve = [&](Carver &c, float *&q, int32_t *&t, anrag_candidate *&o, int32_t *&n) {
-        q = dense ? c.take<float>((int64_t)n_queries * idx->dim) : nullptr;
-        t = total_terms > 0 ? c.take<int32_t>(total_terms) : nullptr;
-        o = c.take<anrag_candidate>((int64_t)n_queries * top_n);
-        n = c.take<int32_t>(n_queries);
-    };
     float *d_q = nullptr;
     int32_t *d_t = nullptr, *d_cnt = nullptr;
     anrag_candidate *d_out = nullptr;
-    carve(measure, d_q, d_t, d_out, d_cnt);
-    if ((rc = ensure_pool(idx, idx->call_pool, measure.at))) return rc;
-    Carver cv(idx->call_pool.p);
-    carve(cv, d_q, d_t, d_out, d_cnt);
+    rc = carve_pool(idx, idx->call_pool, 0, [&](Carver &c) {
+        d_q = dense ? c.take<float>((int64_t)n_queries * idx->dim) : nullptr;
+        d_t = total_terms > 0 ? c.take<int32_t>(total_terms) : nullptr;
+        d_out = c.take<anrag_candidate>((int64_t)n_queries * top_n);
+        d_cnt = c.take<int32_t>(n_queries);
+    });
+    if (rc) return rc;
     std::vector<anrag_candidate> h_out;
     std::vector<int32_t> h_cnt;
     auto body = [&]() -> int {
@@ -1563,31 +1520,48 @@ int anrag_debug_prefilter_read(anrag_index *idx, int32_t *out_form, int64_t *out
     return ANRAG_OK;
 }
 
+// a NaN pattern other than the one the kernels write (0x7FC00000): what a diagnostic pre-fills a buffer with
+static bool foreign_nan(uint32_t bits) {
+    return (bits & 0x7F800000u) == 0x7F800000u && (bits & 0x007FFFFFu) != 0 && bits != 0x7FC00000u;
+}
+
+// What the diagnostic scans share: the checks of one scan launch's operands, then -- behind sync_all, which frees list
+// sets 0 .. n_queries - 1 and the staging buffers -- the allow list and the queries staged on the primary stream, query i
+// on list set i.
+static int debug_scan_prologue(anrag_index *idx, const float *queries, int32_t n_queries, int32_t k,
+                               const uint8_t *allow_source, int32_t n_sources, uint32_t sentinel, const char *sentinel_text,
+                               bool also_ok, const char *also_text, const uint32_t **d_allow, int *sets, const float **qs) {
+    ANRAG_REQUIRE(n_queries >= 1 && n_queries <= kScanGroupMax, "a scan launch takes 1..%d queries", kScanGroupMax);
+    ANRAG_REQUIRE(k >= 1 && k <= ANRAG_FUSED_K_MAX, "1 <= k <= %d", ANRAG_FUSED_K_MAX);
+    ANRAG_REQUIRE(!(allow_source && !idx->d_dense_src), "a source filter needs source ids (anrag_dense_load)");
+    ANRAG_REQUIRE(foreign_nan(sentinel), "%s", sentinel_text);
+    ANRAG_REQUIRE(also_ok, "%s", also_text);  // the entry's own last check
+    if (int rc = sync_all(idx)) return rc;
+    hipStream_t st = idx->primary;
+    uint32_t *h_bits = reinterpret_cast<uint32_t *>(idx->h_pinned);
+    if (int rc = stage_allow(st, allow_source, n_sources, h_bits, idx->d_allow_a, d_allow)) return rc;
+    ANRAG_HIP(hipMemcpyAsync(idx->d_query, queries, (size_t)n_queries * idx->dim * sizeof(float), hipMemcpyHostToDevice, st));
+    for (int i = 0; i < n_queries; ++i) {
+        sets[i] = i;
+        qs[i] = idx->d_query + (int64_t)i * idx->dim;
+    }
+    return ANRAG_OK;
+}
+
 int anrag_debug_prefilter_bounds(anrag_index *idx, const float *queries, int32_t n_queries, int32_t k,
                                  const uint8_t *allow_source, int32_t n_sources, uint32_t sentinel, float *out_hi,
                                  float *out_threshold) {
     ANRAG_ENTER(idx);
     ANRAG_REQUIRE(idx->d_emb != nullptr && idx->pf_on, "the dense prefilter is off");
     ANRAG_REQUIRE(queries && out_hi && out_threshold, "NULL operand");
-    ANRAG_REQUIRE(n_queries >= 1 && n_queries <= kScanGroupMax, "a scan launch takes 1..%d queries", kScanGroupMax);
-    ANRAG_REQUIRE(k >= 1 && k <= ANRAG_FUSED_K_MAX, "1 <= k <= %d", ANRAG_FUSED_K_MAX);
-    ANRAG_REQUIRE(!(allow_source && !idx->d_dense_src), "a source filter needs source ids (anrag_dense_load)");
-    ANRAG_REQUIRE((sentinel & 0x7F800000u) == 0x7F800000u && (sentinel & 0x007FFFFFu) != 0 && sentinel != 0x7FC00000u,
-                  "the sentinel must be a NaN pattern other than the kernel's 0x7FC00000");
-    int rc = sync_all(idx);  // list sets 0 .. n_queries - 1 and the staging buffers are free behind this
-    if (rc) return rc;
-    hipStream_t st = idx->primary;
     const uint32_t *d_allow = nullptr;
-    if ((rc = stage_allow(idx, st, allow_source, n_sources, idx->d_allow_a, reinterpret_cast<uint32_t *>(idx->h_pinned),
-                          &d_allow)))
-        return rc;
-    ANRAG_HIP(hipMemcpyAsync(idx->d_query, queries, (size_t)n_queries * idx->dim * sizeof(float), hipMemcpyHostToDevice, st));
     int sets[kScanGroupMax];
     const float *qs[kScanGroupMax];
-    for (int i = 0; i < n_queries; ++i) {
-        sets[i] = i;
-        qs[i] = idx->d_query + (int64_t)i * idx->dim;
-    }
+    int rc = debug_scan_prologue(idx, queries, n_queries, k, allow_source, n_sources, sentinel,
+                                 "the sentinel must be a NaN pattern other than the kernel's 0x7FC00000", true, "", &d_allow,
+                                 sets, qs);
+    if (rc) return rc;
+    hipStream_t st = idx->primary;
     ANRAG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(idx->d_pf_hi), (int)sentinel,
                                 (size_t)n_queries * idx->pf_hi_stride, st));
     ANRAG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(idx->d_pf_thr), (int)sentinel, (size_t)n_queries, st));
@@ -1614,31 +1588,19 @@ int anrag_debug_dense_lists(anrag_index *idx, const float *queries, int32_t n_qu
     *out_n_lists = n_lists;
     if (!out_scores && !out_rows) return ANRAG_OK;  // the size question alone
     ANRAG_REQUIRE(queries && out_scores && out_rows, "NULL operand");
-    ANRAG_REQUIRE(n_queries >= 1 && n_queries <= kScanGroupMax, "a scan launch takes 1..%d queries", kScanGroupMax);
-    ANRAG_REQUIRE(k >= 1 && k <= ANRAG_FUSED_K_MAX, "1 <= k <= %d", ANRAG_FUSED_K_MAX);
-    ANRAG_REQUIRE(!(allow_source && !idx->d_dense_src), "a source filter needs source ids (anrag_dense_load)");
-    ANRAG_REQUIRE((score_sentinel & 0x7F800000u) == 0x7F800000u && (score_sentinel & 0x007FFFFFu) != 0 &&
-                      score_sentinel != 0x7FC00000u,
-                  "the score sentinel must be a NaN pattern other than 0x7FC00000");
-    ANRAG_REQUIRE(row_sentinel != kNoRow && (int64_t)row_sentinel >= idx->n_rows,
-                  "the row sentinel must be neither a row of the corpus nor the empty slot's 0xFFFFFFFF");
-    int rc = sync_all(idx);  // list sets 0 .. n_queries - 1 and the staging buffers are free behind this
+    const uint32_t *d_allow = nullptr;
+    int sets[kScanGroupMax];
+    const float *qs[kScanGroupMax];
+    int rc = debug_scan_prologue(idx, queries, n_queries, k, allow_source, n_sources, score_sentinel,
+                                 "the score sentinel must be a NaN pattern other than 0x7FC00000",
+                                 row_sentinel != kNoRow && (int64_t)row_sentinel >= idx->n_rows,
+                                 "the row sentinel must be neither a row of the corpus nor the empty slot's 0xFFFFFFFF",
+                                 &d_allow, sets, qs);
     if (rc) return rc;
     hipStream_t st = idx->primary;
     const bool pf_stats = idx->pf_on && idx->d_pf_survivors;
     unsigned long long survivors = 0;
     if (pf_stats) ANRAG_HIP(hipMemcpy(&survivors, idx->d_pf_survivors, sizeof(survivors), hipMemcpyDeviceToHost));
-    const uint32_t *d_allow = nullptr;
-    if ((rc = stage_allow(idx, st, allow_source, n_sources, idx->d_allow_a, reinterpret_cast<uint32_t *>(idx->h_pinned),
-                          &d_allow)))
-        return rc;
-    ANRAG_HIP(hipMemcpyAsync(idx->d_query, queries, (size_t)n_queries * idx->dim * sizeof(float), hipMemcpyHostToDevice, st));
-    int sets[kScanGroupMax];
-    const float *qs[kScanGroupMax];
-    for (int i = 0; i < n_queries; ++i) {
-        sets[i] = i;
-        qs[i] = idx->d_query + (int64_t)i * idx->dim;
-    }
     const size_t set_len = (size_t)kMaxScanLists * kListLen;
     ANRAG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(idx->d_blk_score_f32), (int)score_sentinel,
                                 (size_t)n_queries * set_len, st));

@@ -12,6 +12,7 @@
 
 #include "anrag.h"
 #include "host_slots.hpp"
+#include "scan_lanes.hpp"
 
 namespace anrag {
 
@@ -20,13 +21,11 @@ constexpr int kListLen = 64;         // one top-k slot per lane (ANRAG_FUSED_K_M
 constexpr int kScanThreads = 256;    // 4 waves: one scan workgroup per CU (sweep: profiles/r01_scan_config_sweep.txt)
 constexpr int kScanWaves = kScanThreads / kWave;
 constexpr int kScanGroupMax = 16;  // queries one scan / K3 / tail launch can carry (dense_scan.hip, bm25.hip, tail.hip)
-constexpr int kPipeSlots = 32;     // queries in flight in the hybrid pipeline (list sets, events): four exchange
-                                   // groups of 8, so a slow collective on the communication stream (which the tails
-                                   // queue behind) does not stall the scans two groups later
-constexpr int kScanLanesMax = 4;     // scan streams that single dense queries rotate over (api.hip)
+// kPipeSlots (queries in flight, list sets) and kScanLanesMax: scan_lanes.hpp
 constexpr int kMaxScanBlocks = 256;  // one per CU
 constexpr int kMaxScanLists = kMaxScanBlocks * kScanWaves;  // K1 leaves one sorted list per WAVE (the tail merges them)
 constexpr uint32_t kNoRow = 0xFFFFFFFFu;
+constexpr int kAllowWords = 2048;    // an allow bitmap: one bit per source id (65536), as the kernels stage it in LDS
 
 void set_error(const char *fmt, ...);
 
@@ -108,6 +107,34 @@ struct Carver {
     }
 };
 
+// Lay a call's buffers out in a grow-only block: `layout(Carver &)` runs once to measure, `reserve(bytes, &base)` makes
+// the block hold that much, `layout` runs again on the block itself.
+template <class Reserve, class Layout>
+inline int carve_block(Reserve &&reserve, Layout &&layout) {
+    Carver measure(nullptr);
+    layout(measure);
+    char *base = nullptr;
+    if (int rc = reserve(measure.at, &base)) return rc;
+    Carver real(base);
+    layout(real);
+    return ANRAG_OK;
+}
+
+// allow list (one byte per source, NOT NULL) -> bitmap of kAllowWords words in host memory
+int pack_allow_bits(const uint8_t *allow, int32_t n_sources, uint32_t *h_bits);
+
+// k candidate records -> the caller's arrays; *out_count = the records that name a document (padding has doc -1)
+template <typename S>
+inline void unpack_records(const anrag_candidate *rec, int32_t k, int64_t *out_doc, S *out_score, int32_t *out_count) {
+    int32_t cnt = 0;
+    for (int32_t i = 0; i < k; ++i) {
+        out_doc[i] = rec[i].doc;
+        out_score[i] = (S)rec[i].score;
+        if (rec[i].doc >= 0) ++cnt;
+    }
+    *out_count = cnt;
+}
+
 }  // namespace anrag
 
 // One GPU's shard.  Everything the kernels touch lives in HBM for the index's lifetime.
@@ -134,14 +161,11 @@ struct anrag_index {
         hipStream_t st = nullptr;
         bool pending = false;         // a scan whose lists have not been merged yet
         anrag::PendingTail tail{};
-        uint64_t count = 0;           // queries this lane has taken since the last drain
         hipEvent_t ev[4] = {};        // backpressure: recorded every (slots per lane / 4) queries
     };
     ScanLane lane[anrag::kScanLanesMax];
     int n_lanes = 1;                  // configured (ANRAG_SCAN_LANES)
-    int lanes_in_use = 1;             // ... and what the current run of single queries uses (1 for big corpora)
-    uint64_t lane_rr = 0;
-    bool lanes_active = false;
+    anrag::ScanLanes lanes;           // which lane and list set the next query takes, which event covers the set's reuse
     hipEvent_t ev_order = nullptr;  // anrag_index_wait_stream / anrag_index_signal_stream
     // host-pointer hybrid queries (anrag_hybrid_search): per-slot staging, so that callers on several threads
     // overlap -- a caller holds the index lock while it enqueues, not while it waits for its result
@@ -187,7 +211,7 @@ struct anrag_index {
     uint32_t *d_blk_row_b = nullptr;
     float *d_query = nullptr;           // staged queries
     int64_t query_cap = 0;
-    uint32_t *d_allow_a = nullptr, *d_allow_b = nullptr;  // staged allow bitmaps (2048 words each)
+    uint32_t *d_allow_a = nullptr, *d_allow_b = nullptr;  // staged allow bitmaps (kAllowWords each)
     int32_t *d_terms = nullptr;         // staged term ids
     anrag_candidate *d_cand_a = nullptr, *d_cand_out = nullptr;
     int64_t cand_cap = 0;
@@ -285,6 +309,17 @@ int drain_profile(anrag_index *idx);
 int sync_all(anrag_index *idx);         // wait for the index's three streams
 int settle_pipeline(anrag_index *idx);  // ... only when pipeline queries may be outstanding
 int ensure_pool(anrag_index *idx, DevicePool &pool, int64_t bytes);  // grow-only (contents are NOT kept)
+// carve_block in one of the index's pools, grown to the layout's size plus `slack`
+template <class Layout>
+inline int carve_pool(anrag_index *idx, DevicePool &pool, int64_t slack, Layout &&layout) {
+    return carve_block(
+        [&](int64_t bytes, char **base) {
+            const int rc = ensure_pool(idx, pool, bytes + slack);
+            *base = pool.p;
+            return rc;
+        },
+        layout);
+}
 
 // ---- kernel launchers (each enqueues on `stream`, never syncs)
 int dense_scan_grid(const anrag_index *idx);

@@ -12,6 +12,7 @@
 //   * re-sizing the staging (another corpus dimension) waits until no slot is busy.
 // The device side is behind a Backend (below), so this file builds with plain g++ and runs under ThreadSanitizer
 // with a fake device: tests/native/host_slots_tsan.cpp, driven by tests/test_host_slots_tsan.py.
+// scan_lanes.hpp is the sibling header for the scan lanes' bookkeeping.
 #pragma once
 #include <condition_variable>
 #include <cstdint>

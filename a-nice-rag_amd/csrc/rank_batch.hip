@@ -1170,9 +1170,7 @@ extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int3
         ld[l].stride = (leg_rows[l] + 63) / 64 * 64;
         if (g.allow_source) {
             ld[l].allow = cv.take<uint32_t>(2048);
-            std::fill(h_bits.begin(), h_bits.end(), 0u);
-            for (int32_t s = 0; s < g.n_sources; ++s)
-                if (g.allow_source[s]) h_bits[s >> 5] |= 1u << (s & 31);
+            if (int rc = pack_allow_bits(g.allow_source, g.n_sources, h_bits.data())) return rc;
             ANRAG_HIP(hipMemcpyAsync(ld[l].allow, h_bits.data(), 2048 * 4, hipMemcpyHostToDevice, st));
             ANRAG_HIP(hipStreamSynchronize(st));  // h_bits is reused by the next leg
         }

@@ -261,8 +261,7 @@ anrag::GroupView anrag::shard_group_view(anrag_shard_group *g) {
 
 namespace {
 
-constexpr size_t kAllowBytes = 2048 * sizeof(uint32_t);
-constexpr size_t kPinTerms = 2 * kAllowBytes;
+constexpr size_t kPinTerms = 2 * kAllowWords * sizeof(uint32_t);  // behind the two allow bitmaps
 constexpr size_t kPinOut = kPinTerms + kGroupTermsMax * sizeof(int32_t);
 constexpr size_t kPinCount = kPinOut + (size_t)kGroupChunk * 2 * kListLen * sizeof(anrag_candidate);
 constexpr size_t kPinBytes = kPinCount + (size_t)kGroupChunk * sizeof(int32_t);
@@ -316,14 +315,6 @@ void destroy(anrag_shard_group *g) {
     delete g;
 }
 
-int stage_bits(const uint8_t *allow, int32_t n_sources, uint32_t *h_bits) {
-    ANRAG_REQUIRE(n_sources >= 0 && n_sources <= 65536, "n_sources %d out of range [0, 65536]", n_sources);
-    memset(h_bits, 0, kAllowBytes);
-    for (int32_t s = 0; s < n_sources; ++s)
-        if (allow[s]) h_bits[s >> 5] |= 1u << (s & 31);
-    return ANRAG_OK;
-}
-
 // One call's worth of the hot route.  mode kGroupFuse: the answer of anrag_hybrid_search per query; kGroupDense /
 // kGroupBm25: the k records of the one leg.  `queries` NULL = no dense leg; `term_offsets` NULL = no query has terms.
 // h_out [n_queries][width] / h_cnt [n_queries]: width = top_n (fuse) or k.
@@ -359,38 +350,33 @@ int run_chunk(anrag_shard_group *g, const HotCall &c, int32_t q0, int32_t nq, bo
         }
     }
     const uint32_t *h_aa = reinterpret_cast<const uint32_t *>(g->h_pin);
-    const uint32_t *h_ab = reinterpret_cast<const uint32_t *>(g->h_pin + kAllowBytes);
+    const uint32_t *h_ab = h_aa + kAllowWords;
     float *d_q[ANRAG_GROUP_MAX_SHARDS] = {};
     int32_t *d_t[ANRAG_GROUP_MAX_SHARDS] = {};
     anrag_candidate *d_out = nullptr;
     int32_t *d_cnt = nullptr;
     int rc;
     for (int32_t i = 0; i < g->n; ++i) {  // operands up: the query vectors on the scan's stream, the rest on K3's
-        Carver measure(nullptr), *cv = &measure;
-        auto carve = [&]() {
-            d_q[i] = dense_leg ? cv->take<float>((int64_t)nq * g->dim) : nullptr;
-            d_t[i] = n_terms > 0 ? cv->take<int32_t>(n_terms) : nullptr;
-            if (i == 0) {
-                d_out = cv->take<anrag_candidate>((int64_t)nq * width);
-                d_cnt = cv->take<int32_t>(nq);
-            }
-        };
-        carve();
-        char *pool = nullptr;
-        if ((rc = reserve_call_pool(g->shard[i], measure.at + 256, &pool))) return rc;
-        Carver real(pool);
-        cv = &real;
-        carve();
+        rc = carve_block([&](int64_t bytes, char **pool) { return reserve_call_pool(g->shard[i], bytes + 256, pool); },
+                         [&](Carver &cv) {
+                             d_q[i] = dense_leg ? cv.take<float>((int64_t)nq * g->dim) : nullptr;
+                             d_t[i] = n_terms > 0 ? cv.take<int32_t>(n_terms) : nullptr;
+                             if (i == 0) {
+                                 d_out = cv.take<anrag_candidate>((int64_t)nq * width);
+                                 d_cnt = cv.take<int32_t>(nq);
+                             }
+                         });
+        if (rc) return rc;
         DeviceGuard guard(g->device[i]);
         anrag_index *sh = g->shard[i];
         if (dense_leg)
             ANRAG_HIP(hipMemcpyAsync(d_q[i], src_q, (size_t)nq * g->dim * sizeof(float), hipMemcpyHostToDevice, sh->primary));
         if (c.allow_dense)
-            ANRAG_HIP(hipMemcpyAsync(g->d_allow_a[i], h_aa, kAllowBytes, hipMemcpyHostToDevice, sh->primary));
+            ANRAG_HIP(hipMemcpyAsync(g->d_allow_a[i], h_aa, kAllowWords * sizeof(uint32_t), hipMemcpyHostToDevice, sh->primary));
         if (n_terms > 0)
             ANRAG_HIP(hipMemcpyAsync(d_t[i], src_t, (size_t)n_terms * sizeof(int32_t), hipMemcpyHostToDevice, sh->secondary));
         if (c.allow_bm25)
-            ANRAG_HIP(hipMemcpyAsync(g->d_allow_b[i], h_ab, kAllowBytes, hipMemcpyHostToDevice, sh->secondary));
+            ANRAG_HIP(hipMemcpyAsync(g->d_allow_b[i], h_ab, kAllowWords * sizeof(uint32_t), hipMemcpyHostToDevice, sh->secondary));
     }
     hipStream_t home = g->shard[0]->fusion;
     for (int32_t e0 = 0; e0 < nq; e0 += kGroupQueries) {
@@ -483,9 +469,9 @@ int run_hot(anrag_shard_group *g, const HotCall &c, std::vector<anrag_candidate>
         ANRAG_REQUIRE(c.mode != kGroupFuse || dense_leg, "hybrid search with neither a dense nor a BM25 leg");
     }
     int rc;
-    if (c.allow_dense && (rc = stage_bits(c.allow_dense, c.n_dense_sources, reinterpret_cast<uint32_t *>(g->h_pin)))) return rc;
-    if (c.allow_bm25 && (rc = stage_bits(c.allow_bm25, c.n_bm25_sources, reinterpret_cast<uint32_t *>(g->h_pin + kAllowBytes))))
-        return rc;
+    uint32_t *h_bits = reinterpret_cast<uint32_t *>(g->h_pin);
+    if (c.allow_dense && (rc = pack_allow_bits(c.allow_dense, c.n_dense_sources, h_bits))) return rc;
+    if (c.allow_bm25 && (rc = pack_allow_bits(c.allow_bm25, c.n_bm25_sources, h_bits + kAllowWords))) return rc;
     const int32_t width = c.mode == kGroupFuse ? c.top_n : c.k;
     h_out.resize((size_t)c.n_queries * width);
     h_cnt.resize(c.n_queries);
@@ -512,7 +498,7 @@ int run_batched(anrag_shard_group *g, const float *queries, int32_t n_queries, i
                 int32_t n_sources, int64_t *out_doc, float *out_score, int32_t *out_count, std::vector<int32_t> &redo) {
     const int32_t S = g->n, dim = g->dim;
     int rc;
-    if (allow_source && (rc = stage_bits(allow_source, n_sources, reinterpret_cast<uint32_t *>(g->h_pin)))) return rc;
+    if (allow_source && (rc = pack_allow_bits(allow_source, n_sources, reinterpret_cast<uint32_t *>(g->h_pin)))) return rc;
     // the shards' own locks, in address order (shard_group_rank.hip): their workspaces and profiling state are also
     // reached through the borrowed handles
     std::vector<anrag_index *> owners(g->shard, g->shard + S);
@@ -535,30 +521,25 @@ int run_batched(anrag_shard_group *g, const float *queries, int32_t n_queries, i
             return ANRAG_ERR_HIP;
         }
         if ((rc = settle_pipeline(sh))) return rc;
-        Carver measure(nullptr), *cv = &measure;
-        auto carve = [&]() {
-            d_q[i] = cv->take<float>((int64_t)kBatchedQueries * dim);
+        rc = carve_pool(sh, sh->call_pool, 256, [&](Carver &cv) {  // grow-only; nothing of the shard's is in flight
+            d_q[i] = cv.take<float>((int64_t)kBatchedQueries * dim);
             for (int b = 0; b < kBatchedBlocks; ++b) {
-                d_rec[i][b] = cv->take<anrag_candidate>((int64_t)kBatchedQueries * k);
-                d_flag[i][b] = cv->take<int32_t>(kBatchedQueries);
+                d_rec[i][b] = cv.take<anrag_candidate>((int64_t)kBatchedQueries * k);
+                d_flag[i][b] = cv.take<int32_t>(kBatchedQueries);
             }
             if (i == 0 && S > 1) {
-                d_out = cv->take<anrag_candidate>((int64_t)kBatchedQueries * k);
-                d_cnt = cv->take<int32_t>(kBatchedQueries);
-                d_oflag = cv->take<int32_t>(kBatchedQueries);
+                d_out = cv.take<anrag_candidate>((int64_t)kBatchedQueries * k);
+                d_cnt = cv.take<int32_t>(kBatchedQueries);
+                d_oflag = cv.take<int32_t>(kBatchedQueries);
             }
-        };
-        carve();
-        if ((rc = ensure_pool(sh, sh->call_pool, measure.at + 256))) return rc;  // grow-only; nothing of the shard's is in flight
-        Carver real(sh->call_pool.p);
-        cv = &real;
-        carve();
+        });
+        if (rc) return rc;
         // K2's workspace for both pass sizes of the call (the sample grows when a pass has 128 queries or fewer): sized
         // here, where nothing is in flight, so that no pass replaces it under the one before
         if (n_chunks > 1 && (rc = reserve_dense_batched(sh, sh->primary, kBatchedQueries, k))) return rc;
         if ((rc = reserve_dense_batched(sh, sh->primary, tail_nq, k))) return rc;
         if (allow_source)
-            ANRAG_HIP(hipMemcpyAsync(g->d_allow_a[i], g->h_pin, kAllowBytes, hipMemcpyHostToDevice, sh->primary));
+            ANRAG_HIP(hipMemcpyAsync(g->d_allow_a[i], g->h_pin, kAllowWords * sizeof(uint32_t), hipMemcpyHostToDevice, sh->primary));
         return ANRAG_OK;
     };
     hipStream_t home = g->shard[0]->primary;
@@ -641,14 +622,9 @@ int run_batched(anrag_shard_group *g, const float *queries, int32_t n_queries, i
             }
             const anrag_candidate *rec = pin_rec(b);
             for (int32_t qi = 0; qi < nq; ++qi) {
-                int32_t cnt = 0;
-                for (int32_t j = 0; j < k; ++j) {
-                    const anrag_candidate &r = rec[(size_t)qi * k + j];
-                    out_doc[(int64_t)(q0 + qi) * k + j] = r.doc;
-                    out_score[(int64_t)(q0 + qi) * k + j] = (float)r.score;
-                    if (r.doc >= 0) ++cnt;
-                }
-                out_count[q0 + qi] = S > 1 ? pin_cnt(b)[qi] : cnt;
+                const int64_t at = (int64_t)(q0 + qi) * k;
+                unpack_records(rec + (size_t)qi * k, k, out_doc + at, out_score + at, out_count + q0 + qi);
+                if (S > 1) out_count[q0 + qi] = pin_cnt(b)[qi];  // the merge kernel's own count
                 if (pin_flag(b)[qi] != 0) redo.push_back(q0 + qi);
             }
             g->b_passes += 1;
@@ -712,14 +688,14 @@ int anrag_shard_group_create(const int32_t *devices, int32_t n_shards, anrag_sha
             DeviceGuard guard(g->device[i]);
             Carver measure(nullptr);
             measure.take<anrag_candidate>(kSlabRecords);
-            measure.take<uint32_t>(2048);
-            measure.take<uint32_t>(2048);
+            measure.take<uint32_t>(kAllowWords);
+            measure.take<uint32_t>(kAllowWords);
             ANRAG_HIP(counted_malloc(&g->d_block[i], (size_t)measure.at));
             g->own_bytes += measure.at;
             Carver cv(g->d_block[i]);
             g->d_slab[i] = cv.take<anrag_candidate>(kSlabRecords);
-            g->d_allow_a[i] = cv.take<uint32_t>(2048);
-            g->d_allow_b[i] = cv.take<uint32_t>(2048);
+            g->d_allow_a[i] = cv.take<uint32_t>(kAllowWords);
+            g->d_allow_b[i] = cv.take<uint32_t>(kAllowWords);
             if (i > 0) {  // the home shard's records are ordered by its own streams
                 for (hipEvent_t &e : g->ev_cand[i]) ANRAG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
                 for (hipEvent_t &e : g->ev_pass[i]) ANRAG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));

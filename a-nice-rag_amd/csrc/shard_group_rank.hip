@@ -387,9 +387,7 @@ extern "C" int anrag_shard_group_rank_batch(const anrag_group_rank_leg *legs, in
     for (int l = 0; l < n_legs; ++l) {
         const anrag_group_rank_leg &g = legs[l];
         if (g.allow_source) {
-            std::fill(h_bits.begin(), h_bits.end(), 0u);
-            for (int32_t s = 0; s < g.n_sources; ++s)
-                if (g.allow_source[s]) h_bits[s >> 5] |= 1u << (s & 31);
+            if (int rc = pack_allow_bits(g.allow_source, g.n_sources, h_bits.data())) return rc;
             for (int32_t s = 0; s < ld[l].n_shards; ++s) {
                 ShardDev &sd = ld[l].sh[s];
                 DeviceGuard guard(sd.device);
