@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ANRAG_LIB") or os.path.join(_HERE, "libanrag.so")
 
 OK = 0
-ERR_UNSUPPORTED = -6  # the route exists for one index, not for a shard group: fatal, never "log and return empty"
+ERR_UNSUPPORTED = -6  # the route exists for one index, not for a shard group (or not for this dimension): fatal, never "log and return empty"
 FUSED_K_MAX = 64
 GROUP_MAX_SHARDS = 16
 KERNEL_DENSE_SCAN, KERNEL_DENSE_BATCHED, KERNEL_BM25, KERNEL_SELECT, KERNEL_WRRF = range(5)
@@ -72,6 +72,8 @@ _SIGNATURES = {
     "anrag_dense_load": [_p, _p, _i64, _i32, _p, _p, _i64],
     "anrag_dense_search": [_p, _p, _i32, _i32, _p, _i32, _p, _p, _p],
     "anrag_dense_search_f64": [_p, _p, _i32, _p, _i32, _p, _p, _p],
+    "anrag_set_dense_f64_scan": [_p, _i32],
+    "anrag_dense_f64_stats": [_p, C.POINTER(_i64), C.POINTER(_i64)],
     "anrag_dense_search_device": [_p, _p, _i32, _i32, _p, _p],
     "anrag_dense_search_batch_device": [_p, _p, _i32, _i32, _p, _p, _p],
     "anrag_set_batched_precision": [_p, _i32],
@@ -85,6 +87,7 @@ _SIGNATURES = {
     "anrag_bm25_scores": [_p, _p, _i32, _p],
     "anrag_wrrf": [_p, _p, _p, _p, _i32, _f64, _i32, _p, _p, _p],
     "anrag_hybrid_search": [_p, _p, _p, _i32, _i32, _f64, _f64, _f64, _i32, _p, _i32, _p, _i32, _p, _p, _p],
+    "anrag_hybrid_search_f64": [_p, _p, _p, _i32, _i32, _f64, _f64, _f64, _i32, _p, _i32, _p, _i32, _p, _p, _p],
     "anrag_hybrid_search_batch": [_p, _p, _p, _p, _i32, _i32, _f64, _f64, _f64, _i32, _p, _i32, _p, _i32, _p, _p, _p],
     "anrag_merge_candidates_device": [_p, _p, _i32, _i32, _i64, _p],
     "anrag_hybrid_candidates_device": [_p, _p, _p, _i32, _i32, _p, _p, _p],

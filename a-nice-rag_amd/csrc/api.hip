@@ -267,6 +267,12 @@ static int apply_dense_prefilter(anrag_index *idx) {
     return ANRAG_OK;
 }
 
+// the fp64-query routes' places in h_pinned (1 MiB): the two allow bitmaps first, as everywhere
+constexpr size_t kF64PinOut = 2 * kAllowWords * sizeof(uint32_t);                              // 2 * ANRAG_FUSED_K_MAX records
+constexpr size_t kF64PinCount = kF64PinOut + 2 * ANRAG_FUSED_K_MAX * sizeof(anrag_candidate);  // the fused count
+constexpr size_t kF64PinQuery = 32768;                                                         // 3,072 doubles
+constexpr size_t kF64PinTerms = 65536;                                                         // 4,096 term ids
+
 #define ANRAG_ENTER(idx)                                                   \
     ANRAG_REQUIRE((idx) != nullptr, "index handle is NULL");              \
     std::lock_guard<std::mutex> lock__((idx)->mu);                        \
@@ -357,6 +363,7 @@ static void free_dense(anrag_index *idx) {
     free_dense_prefilter(idx);
     idx->pf_on = false;
     dev_free(idx, idx->d_dense_scores_f64, idx->n_rows);
+    free_dense_f64_lists(idx);
     dev_free(idx, idx->d_emb, idx->n_rows * idx->dim);
     dev_free(idx, idx->d_dense_src, idx->n_rows);
     dev_free(idx, idx->d_dense_doc, idx->n_rows);
@@ -567,7 +574,39 @@ int anrag_dense_search_f64(anrag_index *idx, const double *query, int32_t k, con
     const uint32_t *d_allow = nullptr;
     uint32_t *h_bits = reinterpret_cast<uint32_t *>(idx->h_pinned);
     if ((rc = stage_allow(st, allow_source, n_sources, h_bits, idx->d_allow_a, &d_allow))) return rc;
-    return dense_search_f64(idx, st, query, k, d_allow, out_doc, out_score, out_count);
+    if (k > ANRAG_FUSED_K_MAX || !idx->f64_scan_on || !dense_scan_f64_serves(idx)) {
+        idx->f64_sorted += 1;
+        return dense_search_f64(idx, st, query, k, d_allow, out_doc, out_score, out_count);
+    }
+    // K1D: per-wave fp64 lists, merged by the fp64 tail -- no score array, no sort (same ids, same score bits)
+    if ((rc = ensure_dense_f64_lists(idx)) || (rc = ensure_query_f64(idx))) return rc;
+    char *pin = static_cast<char *>(idx->h_pinned);
+    double *h_query = reinterpret_cast<double *>(pin + kF64PinQuery);
+    anrag_candidate *h_cand = reinterpret_cast<anrag_candidate *>(pin + kF64PinOut);
+    memcpy(h_query, query, (size_t)idx->dim * sizeof(double));
+    ANRAG_HIP(hipMemcpyAsync(idx->d_query_f64, h_query, (size_t)idx->dim * sizeof(double), hipMemcpyHostToDevice, st));
+    if ((rc = launch_dense_scan_f64(idx, st, idx->d_query_f64, k, d_allow))) return rc;
+    if ((rc = launch_tail_f64(idx, st, /*dense*/ true, /*bm25*/ false, k, kTailCandidates, 0, 0, 0, 0, idx->d_cand_out, nullptr)))
+        return rc;
+    ANRAG_HIP(hipMemcpyAsync(h_cand, idx->d_cand_out, (size_t)k * sizeof(anrag_candidate), hipMemcpyDeviceToHost, st));
+    ANRAG_HIP(hipStreamSynchronize(st));
+    unpack_records(h_cand, k, out_doc, out_score, out_count);
+    idx->f64_scanned += 1;
+    return ANRAG_OK;
+}
+
+int anrag_set_dense_f64_scan(anrag_index *idx, int32_t on) {
+    ANRAG_ENTER(idx);
+    ANRAG_REQUIRE(on == 0 || on == 1, "on must be 0 (score array + sort for every k) or 1 (the list scan where it serves)");
+    idx->f64_scan_on = on == 1;
+    return ANRAG_OK;
+}
+
+int anrag_dense_f64_stats(anrag_index *idx, int64_t *scanned, int64_t *sorted) {
+    ANRAG_ENTER(idx);
+    if (scanned) *scanned = idx->f64_scanned;
+    if (sorted) *sorted = idx->f64_sorted;
+    return ANRAG_OK;
 }
 
 int anrag_dense_scores(anrag_index *idx, const float *query, float *out_scores) {
@@ -1268,6 +1307,68 @@ int anrag_hybrid_search(anrag_index *idx, const float *query, const int32_t *ter
     HybridHostQuery q{idx, query, term_ids, n_terms, similarity_k, w_dense, w_bm25, wrrf_k, top_n, allow_dense,
                       n_dense_sources, allow_bm25, n_bm25_sources, out_id, out_score, out_count};
     return host_slot_query(idx->mu, idx->host_ring, q);
+}
+
+// The fused hybrid query for an fp64 query vector (the text path's embedding): K1D, K3 and the fp64 tail in fuse mode on
+// ONE stream in stream order, behind a settled pipeline -- not pipelined on purpose, this query sits behind a remote
+// embedding call.  Everything in list set 0 and the index's own staging buffers, like the host calls it replaces.
+int anrag_hybrid_search_f64(anrag_index *idx, const double *query, const int32_t *term_ids, int32_t n_terms,
+                            int32_t similarity_k, double w_dense, double w_bm25, double wrrf_k, int32_t top_n,
+                            const uint8_t *allow_dense, int32_t n_dense_sources, const uint8_t *allow_bm25,
+                            int32_t n_bm25_sources, int64_t *out_id, double *out_score, int32_t *out_count) {
+    ANRAG_ENTER(idx);
+    ANRAG_REQUIRE(out_id && out_score && out_count, "NULL operand");
+    ANRAG_REQUIRE(similarity_k > 0 && similarity_k <= ANRAG_FUSED_K_MAX, "fused hybrid serves 1 <= similarity_k <= %d",
+                  ANRAG_FUSED_K_MAX);
+    ANRAG_REQUIRE(top_n > 0 && top_n <= 2 * ANRAG_FUSED_K_MAX, "top_n %d out of range", top_n);
+    ANRAG_REQUIRE(!(allow_dense && !idx->d_dense_src) && !(allow_bm25 && !idx->d_bm25_src),
+                  "a source filter needs source ids");
+    ANRAG_REQUIRE(n_terms >= 0 && n_terms <= 4096, "n_terms %d out of range [0, 4096]", n_terms);
+    ANRAG_REQUIRE(n_terms == 0 || term_ids != nullptr, "term_ids is NULL");
+    const bool use_dense = idx->d_emb && w_dense > 0.0;
+    const bool use_bm25 = idx->d_post_doc && w_bm25 > 0.0 && n_terms > 0;
+    ANRAG_REQUIRE(!use_dense || query != nullptr, "query is NULL");
+    ANRAG_REQUIRE(use_dense || use_bm25, "hybrid search with neither a dense nor a BM25 leg");
+    if (use_dense && !dense_scan_f64_serves(idx)) {
+        set_error("fused fp64 hybrid: dim %d is not served by the fp64 list scan (dim %% 4 == 0, dim <= 3072)", idx->dim);
+        return ANRAG_ERR_UNSUPPORTED;
+    }
+    int rc;
+    if ((rc = settle_pipeline(idx))) return rc;  // (also launches the lanes' pending merges and waits for them)
+    if ((rc = ensure_common_workspace(idx)) || (rc = ensure_dense_f64_lists(idx)) || (rc = ensure_query_f64(idx))) return rc;
+    hipStream_t st = idx->primary;
+    char *pin = static_cast<char *>(idx->h_pinned);
+    const uint32_t *d_ad = nullptr, *d_ab = nullptr;
+    if ((rc = stage_allow(st, allow_dense, n_dense_sources, reinterpret_cast<uint32_t *>(pin), idx->d_allow_a, &d_ad))) return rc;
+    if ((rc = stage_allow(st, allow_bm25, n_bm25_sources, reinterpret_cast<uint32_t *>(pin) + kAllowWords, idx->d_allow_b, &d_ab)))
+        return rc;
+    if (use_dense) {
+        memcpy(pin + kF64PinQuery, query, (size_t)idx->dim * sizeof(double));
+        ANRAG_HIP(hipMemcpyAsync(idx->d_query_f64, pin + kF64PinQuery, (size_t)idx->dim * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    if (use_bm25) {
+        memcpy(pin + kF64PinTerms, term_ids, (size_t)n_terms * sizeof(int32_t));
+        ANRAG_HIP(hipMemcpyAsync(idx->d_terms, pin + kF64PinTerms, (size_t)n_terms * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    }
+    if (use_dense && (rc = launch_dense_scan_f64(idx, st, idx->d_query_f64, similarity_k, d_ad))) return rc;
+    if (use_bm25 && (rc = launch_bm25_lists(idx, st, idx->d_terms, n_terms, similarity_k, d_ab, nullptr, 0))) return rc;
+    int32_t *d_count = dense_f64_count(idx);
+    if ((rc = launch_tail_f64(idx, st, use_dense, use_bm25, similarity_k, kTailFuse, w_dense, w_bm25, wrrf_k, top_n,
+                              idx->d_cand_out, d_count)))
+        return rc;
+    const anrag_candidate *h_cand = reinterpret_cast<const anrag_candidate *>(pin + kF64PinOut);
+    const int32_t *h_count = reinterpret_cast<const int32_t *>(pin + kF64PinCount);
+    ANRAG_HIP(hipMemcpyAsync(pin + kF64PinOut, idx->d_cand_out, (size_t)top_n * sizeof(anrag_candidate), hipMemcpyDeviceToHost, st));
+    ANRAG_HIP(hipMemcpyAsync(pin + kF64PinCount, d_count, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    ANRAG_HIP(hipStreamSynchronize(st));
+    const int32_t cnt = std::min(*h_count, top_n);
+    for (int32_t i = 0; i < cnt; ++i) {
+        out_id[i] = h_cand[i].doc;
+        out_score[i] = h_cand[i].score;
+    }
+    *out_count = cnt;
+    if (use_dense) idx->f64_scanned += 1;
+    return ANRAG_OK;
 }
 
 // Many hybrid queries from host memory through the device pipeline: operands go up once, the queries are

@@ -221,6 +221,9 @@ struct anrag_index {
     double *d_scores_f64 = nullptr;
     double *d_dense_scores_f64 = nullptr;  // fp64-query dense path: n_rows scores
     double *d_query_f64 = nullptr;
+    double *d_blk_score_f64q = nullptr;    // fp64-query list scan (K1D, dense_scan_f64.hip): ONE set [kMaxScanLists][kListLen]
+    bool f64_scan_on = true;               // anrag_set_dense_f64_scan
+    int64_t f64_scanned = 0, f64_sorted = 0;  // fp64 queries answered by K1D / by the score array + sort
     void *d_sort_tmp = nullptr;
     int64_t sort_tmp_bytes = 0;
     void *d_sort_buf = nullptr;
@@ -386,6 +389,9 @@ int launch_tail(anrag_index *idx, hipStream_t st, int set, bool use_dense, bool 
 int launch_tail_group(anrag_index *idx, hipStream_t st, const int *sets, bool use_dense, const bool *use_bm25, int32_t n,
                       int32_t k, TailMode mode, double w_dense, double w_bm25, double wrrf_k, int32_t top_n,
                       anrag_candidate *const *d_out, int32_t *const *d_count);
+// ... with the dense group merging the fp64 lists of K1D (set 0 for both legs)
+int launch_tail_f64(anrag_index *idx, hipStream_t st, bool use_dense, bool use_bm25, int32_t k, TailMode mode, double w_dense,
+                    double w_bm25, double wrrf_k, int32_t top_n, anrag_candidate *d_out, int32_t *d_count);
 // K1 + tail on one stream (set 0)
 int launch_dense_topk(anrag_index *idx, hipStream_t stream, const float *d_query, int32_t k,
                       const uint32_t *d_allow_bits, anrag_candidate *d_out, float *d_scores_out);
@@ -394,6 +400,15 @@ int launch_dense_scores_f64(anrag_index *idx, hipStream_t st, const double *d_qu
                             double *d_scores_out);
 int dense_search_f64(anrag_index *idx, hipStream_t st, const double *h_query, int32_t k, const uint32_t *d_allow_bits,
                      int64_t *out_doc, double *out_score, int32_t *out_count);
+// K1D, the list-keeping scan of one fp64 query (dense_scan_f64.hip): dim % 4 == 0 up to 3,072, k <= 64.  One sorted fp64
+// list per wave into the fp64 list set, rows into set 0 of d_blk_row_a; launch_tail_f64 merges them (with the BM25
+// lists of set 0).
+bool dense_scan_f64_serves(const anrag_index *idx);
+int ensure_dense_f64_lists(anrag_index *idx);  // allocated by the first such query (counted), freed with the dense buffers
+void free_dense_f64_lists(anrag_index *idx);
+int32_t *dense_f64_count(const anrag_index *idx);  // a device int32 behind the lists: the fused call's count
+int ensure_query_f64(anrag_index *idx);
+int launch_dense_scan_f64(anrag_index *idx, hipStream_t st, const double *d_query, int32_t k, const uint32_t *d_allow_bits);
 // K2: up to 256 queries per pass on the fp32 matrix cores (dense_batched.hip)
 bool batched_path_applies(const anrag_index *idx, int32_t n_queries, int32_t k);
 int launch_dense_batched(anrag_index *idx, hipStream_t st, const float *d_queries, int32_t nq, int32_t k,

@@ -19,8 +19,10 @@ namespace anrag {
 constexpr int kTailThreads = 512;  // 8 waves: 4 per modality
 
 // one workgroup per query of a group (blockIdx.x): the tails of the queries that shared a scan / K3 launch share one too
+// DS: the dense lists' score type -- float (K1, K1F) or double (K1D, the fp64 query's scan)
+template <typename DS>
 struct TailQuery {
-    const float *d_score;     // dense block lists
+    const DS *d_score;        // dense block lists
     const uint32_t *d_row;
     const double *b_score;    // BM25 partition lists
     const uint32_t *b_row;
@@ -29,8 +31,9 @@ struct TailQuery {
     anrag_candidate *out;
     int32_t *count;
 };
+template <typename DS>
 struct TailGroup {
-    TailQuery q[kScanGroupMax];
+    TailQuery<DS> q[kScanGroupMax];
     const int64_t *dense_doc;
     int64_t dense_base;
     const int64_t *bm25_doc;
@@ -38,7 +41,8 @@ struct TailGroup {
     int32_t k, mode, top_n;
     double w_dense, w_bm25, wrrf_k;
 };
-struct TailArgs : TailQuery {
+template <typename DS>
+struct TailArgs : TailQuery<DS> {
     const int64_t *dense_doc;
     int64_t dense_base;
     const int64_t *bm25_doc;
@@ -47,10 +51,10 @@ struct TailArgs : TailQuery {
     double w_dense, w_bm25, wrrf_k;
 };
 
-template <bool GROUPED>
-__global__ __launch_bounds__(kTailThreads) void query_tail_kernel(TailGroup grp) {
-    TailArgs a;
-    static_cast<TailQuery &>(a) = grp.q[GROUPED ? (int)blockIdx.x : 0];  // one query: fixed kernarg offsets
+template <bool GROUPED, typename DS>
+__global__ __launch_bounds__(kTailThreads) void query_tail_kernel(TailGroup<DS> grp) {
+    TailArgs<DS> a;
+    static_cast<TailQuery<DS> &>(a) = grp.q[GROUPED ? (int)blockIdx.x : 0];  // one query: fixed kernarg offsets
     a.dense_doc = grp.dense_doc;
     a.dense_base = grp.dense_base;
     a.bm25_doc = grp.bm25_doc;
@@ -61,7 +65,7 @@ __global__ __launch_bounds__(kTailThreads) void query_tail_kernel(TailGroup grp)
     a.w_dense = grp.w_dense;
     a.w_bm25 = grp.w_bm25;
     a.wrrf_k = grp.wrrf_k;
-    __shared__ float lf_s[4 * kListLen];
+    __shared__ DS lf_s[4 * kListLen];
     __shared__ uint32_t lf_r[4 * kListLen];
     __shared__ double ld_s[4 * kListLen];
     __shared__ uint32_t ld_r[4 * kListLen];
@@ -71,13 +75,14 @@ __global__ __launch_bounds__(kTailThreads) void query_tail_kernel(TailGroup grp)
     __shared__ int32_t s_owner[2 * kListLen];
     __shared__ int32_t s_distinct;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    const int group = wave >> 2, gw = wave & 3;  // group 0: dense (fp32 scores), group 1: BM25 (fp64)
+    const int group = wave >> 2, gw = wave & 3;  // group 0: dense (DS scores), group 1: BM25 (fp64)
     const int k = a.k;
 
-    WaveTopK<float> tf;
+    WaveTopK<DS> tf;
     WaveTopK<double> td;
     tf.init(k);
     td.init(k);
+    if constexpr (sizeof(DS) == sizeof(double)) tf.thr_s = neg_inf_opaque();  // signed scores: wave_topk.hpp
     if (group == 0) {
         if (a.n_dense > 0) merge_lists(tf, a.d_score, a.d_row, a.n_dense, k, gw, 4);
     } else {
@@ -140,15 +145,16 @@ __global__ __launch_bounds__(kTailThreads) void query_tail_kernel(TailGroup grp)
     wrrf_in_block(s_id, s_c, s_score, s_owner, &s_distinct, m, a.top_n, a.out, a.count);
 }
 
-int launch_tail_group(anrag_index *idx, hipStream_t st, const int *sets, bool use_dense, const bool *use_bm25, int32_t n,
-                      int32_t k, TailMode mode, double w_dense, double w_bm25, double wrrf_k, int32_t top_n,
-                      anrag_candidate *const *d_out, int32_t *const *d_count) {
+template <typename DS>
+static int launch_tail_lists(anrag_index *idx, hipStream_t st, const DS *dense_lists, const int *sets, bool use_dense,
+                             const bool *use_bm25, int32_t n, int32_t k, TailMode mode, double w_dense, double w_bm25,
+                             double wrrf_k, int32_t top_n, anrag_candidate *const *d_out, int32_t *const *d_count) {
     ANRAG_REQUIRE(n >= 1 && n <= kScanGroupMax, "tail group of %d queries", n);
-    TailGroup a;
+    TailGroup<DS> a;
     for (int i = 0; i < kScanGroupMax; ++i) {
         const int j = i < n ? i : 0;
-        TailQuery &q = a.q[i];
-        q.d_score = idx->d_blk_score_f32 + (int64_t)sets[j] * kMaxScanLists * kListLen;
+        TailQuery<DS> &q = a.q[i];
+        q.d_score = dense_lists + (int64_t)sets[j] * kMaxScanLists * kListLen;
         q.d_row = idx->d_blk_row_a + (int64_t)sets[j] * kMaxScanLists * kListLen;
         q.n_dense = use_dense ? dense_scan_lists(idx) : 0;
         q.b_score = idx->d_blk_score_f64 + (int64_t)sets[j] * idx->n_parts * kListLen;
@@ -168,10 +174,24 @@ int launch_tail_group(anrag_index *idx, hipStream_t st, const int *sets, bool us
     a.w_bm25 = w_bm25;
     a.wrrf_k = wrrf_k;
     LaunchTimer t(idx, mode == kTailFuse ? ANRAG_KERNEL_WRRF : ANRAG_KERNEL_SELECT, st, n);
-    if (n == 1) query_tail_kernel<false><<<1, kTailThreads, 0, st>>>(a);
-    else query_tail_kernel<true><<<n, kTailThreads, 0, st>>>(a);
+    if (n == 1) query_tail_kernel<false, DS><<<1, kTailThreads, 0, st>>>(a);
+    else query_tail_kernel<true, DS><<<n, kTailThreads, 0, st>>>(a);
     ANRAG_HIP(hipGetLastError());
     return ANRAG_OK;
+}
+
+int launch_tail_group(anrag_index *idx, hipStream_t st, const int *sets, bool use_dense, const bool *use_bm25, int32_t n,
+                      int32_t k, TailMode mode, double w_dense, double w_bm25, double wrrf_k, int32_t top_n,
+                      anrag_candidate *const *d_out, int32_t *const *d_count) {
+    return launch_tail_lists<float>(idx, st, idx->d_blk_score_f32, sets, use_dense, use_bm25, n, k, mode, w_dense, w_bm25,
+                                    wrrf_k, top_n, d_out, d_count);
+}
+
+int launch_tail_f64(anrag_index *idx, hipStream_t st, bool use_dense, bool use_bm25, int32_t k, TailMode mode, double w_dense,
+                    double w_bm25, double wrrf_k, int32_t top_n, anrag_candidate *d_out, int32_t *d_count) {
+    const int set = 0;
+    return launch_tail_lists<double>(idx, st, idx->d_blk_score_f64q, &set, use_dense, &use_bm25, 1, k, mode, w_dense, w_bm25,
+                                     wrrf_k, top_n, &d_out, d_count ? &d_count : nullptr);
 }
 
 int launch_tail(anrag_index *idx, hipStream_t st, int set, bool use_dense, bool use_bm25, int32_t k, TailMode mode,

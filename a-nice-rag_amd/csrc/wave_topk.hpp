@@ -20,6 +20,16 @@ __device__ __forceinline__ float neg_inf<float>() { return -__builtin_huge_valf(
 template <>
 __device__ __forceinline__ double neg_inf<double>() { return -__builtin_huge_val(); }
 
+// -inf as a value the compiler cannot fold.  A WaveTopK<double> whose threshold it keeps in a scalar register pair got
+// that pair initialised with 0 instead of -inf's bits (hipcc 7, gfx950: `s_mov_b64 s[88:89], 0` in the fp64 tail) --
+// harmless for BM25's scores (>= 0: a zero score still passes by the row rule), fatal for dot products, which may be
+// negative: a list whose best score was below zero never got in.  Lists of signed scores start from this.
+__device__ __forceinline__ double neg_inf_opaque() {
+    uint32_t hi = 0xfff00000u, lo = 0u;
+    asm volatile("" : "+s"(hi), "+s"(lo));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
 template <typename S>
 __device__ __forceinline__ bool beats(S s, uint32_t r, S ts, uint32_t tr) {
     return s > ts || (s == ts && r < tr);

@@ -470,6 +470,23 @@ class Index:
                                                    doc.ctypes.data, score.ctypes.data, count.ctypes.data))
         return doc, score, int(count[0])
 
+    F64_SCAN_MAX_DIM = 3072
+
+    def dense_f64_scan_serves(self) -> bool:
+        """The fp64 list scan (and with it `hybrid_search_f64`) serves this index's dimension."""
+        return self.n_rows > 0 and self.dim % 4 == 0 and self.dim <= self.F64_SCAN_MAX_DIM
+
+    def set_dense_f64_scan(self, on: bool = True) -> None:
+        """Route of `dense_search_f64`: the list scan where it serves (default), or the score array + sort for every k
+        (`anrag_set_dense_f64_scan`).  Same ids and score bits on both."""
+        nat.check(self._lib.anrag_set_dense_f64_scan(self.handle, 1 if on else 0))
+
+    def dense_f64_stats(self) -> tuple:
+        """(float64 queries answered by the list scan, by the score array + sort) since the index was created."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        nat.check(self._lib.anrag_dense_f64_stats(self.handle, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def set_batched_precision(self, mode: str = "f32") -> None:
         """"f32": exact f32 MFMA (default).  "bf16x3": split-precision products on the bf16 matrix cores (scores within
         ~3e-5 of f32 for unit-norm vectors)."""
@@ -624,6 +641,26 @@ class Index:
                                                 int(t.size), int(similarity_k), float(w_dense), float(w_bm25),
                                                 float(wrrf_k), int(top_n), nat.ptr(ad), nd, nat.ptr(ab), nb,
                                                 out_id.ctypes.data, out_score.ctypes.data, count.ctypes.data))
+        m = int(count[0])
+        return out_id[:m], out_score[:m]
+
+    def hybrid_search_f64(self, query, term_ids: Sequence[int], similarity_k: int, w_dense: float, w_bm25: float,
+                          wrrf_k: float, top_n: int, allow_dense=None, allow_bm25=None):
+        """`hybrid_search` for one float64 query, its dense leg scored in fp64 (`anrag_hybrid_search_f64`): equals
+        `dense_search_f64` + `bm25_search` + `wrrf` in ids and fused-score bits.  Raises AnragError(-6) for a dimension
+        the fp64 list scan does not serve (`dense_f64_scan_serves`)."""
+        q = np.ascontiguousarray(query, dtype=np.float64).reshape(-1)
+        assert self.n_rows == 0 or q.size == self.dim
+        t = np.ascontiguousarray(term_ids, dtype=np.int32)
+        ad, nd = _allow_bytes(allow_dense)
+        ab, nb = _allow_bytes(allow_bm25)
+        out_id = np.empty(top_n, np.int64)
+        out_score = np.empty(top_n, np.float64)
+        count = np.zeros(1, np.int32)
+        nat.check(self._lib.anrag_hybrid_search_f64(self.handle, q.ctypes.data, nat.ptr(t) if t.size else None,
+                                                    int(t.size), int(similarity_k), float(w_dense), float(w_bm25),
+                                                    float(wrrf_k), int(top_n), nat.ptr(ad), nd, nat.ptr(ab), nb,
+                                                    out_id.ctypes.data, out_score.ctypes.data, count.ctypes.data))
         m = int(count[0])
         return out_id[:m], out_score[:m]
 

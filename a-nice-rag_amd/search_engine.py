@@ -357,18 +357,22 @@ class SearchEngine:
         q = np.asarray(query_embedding)
         if q.ndim == 2 and q.shape[0] != 1:
             return None
-        if q.dtype == np.float64:
-            # the text path's embedding (:157): the reference scores it in fp64 (:129) and so does the method-by-method
-            # route (`anrag_dense_search_f64`); the fused call scores fp32 -- inside 1e-4, but near-ties could order
-            # differently between the two routes of ONE retrieve_documents call: declined, both routes score alike
-            return None
+        f64 = q.dtype == np.float64
         proxy = self._proxy(bm25, bm25_sections)
         pair = FusedPair.of(df, proxy, bm25_section_ids)
+        index = pair.dense.index
+        if f64 and not (isinstance(index, Index) and index.dense_f64_scan_serves()):
+            # the text path's embedding (:157): the reference scores it in fp64 (:129) and so does the method-by-method
+            # route (`anrag_dense_search_f64`).  The fused fp64 call (`anrag_hybrid_search_f64`) scores with the same
+            # bits as that route -- one summation order in both kernels -- so the two routes of ONE retrieve_documents
+            # call cannot order near-ties differently; it exists for a single index and dim % 4 == 0 up to 3,072.  A
+            # shard group or another dimension: declined (the fp32 fused call would score inside 1e-4, not alike)
+            return None
         ad = ab = None
         if filename_type_filter:
             ad = _allow_of(pair.dense, "dense", filename_type_filter)
             ab = _allow_of(proxy, "bm25", filename_type_filter)
-        ids, _ = pair.dense.index.hybrid_search(q.reshape(-1), proxy.term_ids(query_tokens), int(similarity_k),
-                                                float(dense_weight), float(bm25_weight), float(wrrf_k),
-                                                int(common_sections_n), ad, ab)
+        search = index.hybrid_search_f64 if f64 else index.hybrid_search
+        ids, _ = search(q.reshape(-1), proxy.term_ids(query_tokens), int(similarity_k), float(dense_weight),
+                        float(bm25_weight), float(wrrf_k), int(common_sections_n), ad, ab)
         return [pair.id_of_doc[i] for i in ids.tolist()]

@@ -59,7 +59,7 @@ extern "C" {
 #define ANRAG_ERR_STATE (-3)   /* e.g. search before load                        */
 #define ANRAG_ERR_NOMEM (-4)   /* host or device allocation failed               */
 #define ANRAG_ERR_NODEVICE (-5) /* no usable gfx950 device                       */
-#define ANRAG_ERR_UNSUPPORTED (-6) /* the route exists for one index, not for a shard group */
+#define ANRAG_ERR_UNSUPPORTED (-6) /* the route exists for one index, not for a shard group; or not for this dimension */
 
 /* Largest k served by the fused in-register per-wave top-k (one candidate per
  * lane of a 64-wide wavefront).  Larger k (retrieval_eval.py:142-143 uses 12000)
@@ -162,10 +162,23 @@ int anrag_dense_search(anrag_index *idx, const float *queries, int32_t n_queries
  * accumulated in fp64 (fp32 values are exact in fp64), selection by sorting the
  * fp64 score array: any k.  out_score: fp64.  (The fp32 entry points round an
  * fp64 query to fp32 first -- inside the 1e-4 bar, not the reference's bits;
- * the Python shim calls this one when it is handed a float64 query.) */
+ * the Python shim calls this one when it is handed a float64 query.)
+ * k <= ANRAG_FUSED_K_MAX and dim % 4 == 0, dim <= 3072: a streaming scan that keeps per-wave fp64 lists (K1D) and
+ * the list merge answer instead -- no score array, no sort; the same ids and the same score BITS (one summation order
+ * in both kernels).  Its list buffer (512 KB) is allocated by the first such query. */
 int anrag_dense_search_f64(anrag_index *idx, const double *query, int32_t k,
                            const uint8_t *allow_source, int32_t n_sources, int64_t *out_doc,
                            double *out_score, int32_t *out_count);
+
+/* Route of anrag_dense_search_f64 (search_engine.py:157, :129): 1 (default) the list scan wherever it serves, 0 the
+ * score array + sort for every k (A/B measurements, the tests that hold the two routes to the same bits).  The
+ * answers do not depend on it, except that a score of exactly -0.0 ties with +0.0 by row in the list scan and ranks
+ * behind it in the sort. */
+int anrag_set_dense_f64_scan(anrag_index *idx, int32_t on);
+
+/* Cumulative fp64 queries answered by the list scan (anrag_hybrid_search_f64's dense legs included) and by the score
+ * array + sort. */
+int anrag_dense_f64_stats(anrag_index *idx, int64_t *scanned, int64_t *sorted);
 
 /* Same, all operands in HBM, no host sync: d_out is n_queries x k anrag_candidate.
  * n_queries > 1: up to 8 queries share a scan launch (each is still its own pass over the matrix; a workgroup starts
@@ -291,6 +304,20 @@ int anrag_hybrid_search(anrag_index *idx, const float *query, const int32_t *ter
                         int32_t n_dense_sources, const uint8_t *allow_bm25,
                         int32_t n_bm25_sources, int64_t *out_id, double *out_score,
                         int32_t *out_count);
+
+/* anrag_hybrid_search for the fp64 query of the reference's text path (the embedding API's float64 vector,
+ * search_engine.py:157, scored in fp64, :129; then query_rag_retrieval.py:197-220, :304-335, :356-378): same arguments,
+ * outputs, envelope and errors.  The dense leg is the fp64 list scan of anrag_dense_search_f64, so the answer equals
+ * anrag_dense_search_f64 + anrag_bm25_search + anrag_wrrf in ids and fused-score bits -- in ONE call: operands up, the
+ * scan, BM25, merge + WRRF, results down on one stream behind a drained pipeline, one host wait.  Not pipelined (this
+ * query sits behind a remote embedding call); the index lock is held for the whole call.
+ * dim % 4 != 0 or dim > 3072 with a dense leg: ANRAG_ERR_UNSUPPORTED -- the caller composes the three calls. */
+int anrag_hybrid_search_f64(anrag_index *idx, const double *query, const int32_t *term_ids,
+                            int32_t n_terms, int32_t similarity_k, double w_dense, double w_bm25,
+                            double wrrf_k, int32_t top_n, const uint8_t *allow_dense,
+                            int32_t n_dense_sources, const uint8_t *allow_bm25,
+                            int32_t n_bm25_sources, int64_t *out_id, double *out_score,
+                            int32_t *out_count);
 
 /* Same, operands in HBM, nothing syncs the host: d_out receives min(top_n,
  * distinct ids) records in fused order, *d_count that number, complete in
