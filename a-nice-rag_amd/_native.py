@@ -74,6 +74,8 @@ _SIGNATURES = {
     "anrag_dense_search_f64": [_p, _p, _i32, _p, _i32, _p, _p, _p],
     "anrag_set_dense_f64_scan": [_p, _i32],
     "anrag_dense_f64_stats": [_p, C.POINTER(_i64), C.POINTER(_i64)],
+    "anrag_set_dense_f64_prefilter": [_p, _i32],
+    "anrag_dense_f64_prefilter_stats": [_p, C.POINTER(_i64), C.POINTER(_i64)],
     "anrag_dense_search_device": [_p, _p, _i32, _i32, _p, _p],
     "anrag_dense_search_batch_device": [_p, _p, _i32, _i32, _p, _p, _p],
     "anrag_set_batched_precision": [_p, _i32],
@@ -108,6 +110,7 @@ _SIGNATURES = {
     "anrag_debug_alloc_calls": [C.POINTER(_i64)],
     "anrag_debug_prefilter_read": [_p, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i32), _p, _p],
     "anrag_debug_prefilter_bounds": [_p, _p, _i32, _i32, _p, _i32, C.c_uint32, _p, _p],
+    "anrag_debug_prefilter_f64": [_p, _p, _p, C.POINTER(_f64), C.POINTER(_f64)],
     "anrag_debug_dense_lists": [_p, _p, _i32, _i32, _p, _i32, C.c_uint32, C.c_uint32, C.POINTER(_i32), _p, _p],
     "anrag_rank_batch": [_p, _i32, _i32, _i32, _f64, _i32, _i64, _p, _p, _p, _p, _p],
     "anrag_rank_caps": [C.POINTER(_i32), C.POINTER(_i32)],

@@ -273,6 +273,69 @@ constexpr size_t kF64PinCount = kF64PinOut + 2 * ANRAG_FUSED_K_MAX * sizeof(anra
 constexpr size_t kF64PinQuery = 32768;                                                         // 3,072 doubles
 constexpr size_t kF64PinTerms = 65536;                                                         // 4,096 term ids
 
+// ---- the fp64 dense leg: K1D, or the shadow prefilter with K1D's rescoring (K1FD, dense_prefilter_f64.hip)
+static bool dense_f64_prefilter_applies(const anrag_index *idx, int32_t k) {
+    return idx->pf_on && idx->f64_pf_on && k <= ANRAG_FUSED_K_MAX && idx->f64_scan_on && dense_scan_f64_serves(idx);
+}
+
+static double next_up(double x) { return nextafter(x, HUGE_VAL); }  // x >= 0: inf and NaN stay what they are
+
+// q^ = fl32(q) into q32 and the widening w = (delta + gamma64 ||q||) Emax + D 2^-1000 (dense_prefilter_f64.hip), every
+// rounding pushed upward: the two sums of squares are within D 2^-53 of their exact values, so the norms are widened by
+// 2^-42 (D <= 2,048); every other operation is followed by a step to the next double.  A component outside fp32's range
+// or a NaN gives a non-finite w: every row is rescored.
+static double prefilter_f64_widening(const double *q, float *q32, int32_t dim, double emax) {
+    double d2 = 0.0, q2 = 0.0;
+    for (int32_t i = 0; i < dim; ++i) {
+        q32[i] = (float)q[i];
+        const double d = q[i] - (double)q32[i];  // exact
+        d2 += d * d;
+        q2 += q[i] * q[i];
+    }
+    const double widen = 1.0 + 0x1p-42;
+    const double delta = next_up(sqrt(d2) * widen), qn = next_up(sqrt(q2) * widen);
+    const double du = (double)dim * 0x1p-53;  // exact, and so is 1 - du
+    const double g64 = next_up(du / (1.0 - du));
+    double w = next_up(g64 * qn);
+    w = next_up(delta + w);
+    w = next_up(w * emax);
+    return next_up(w + (double)dim * 0x1p-1000);
+}
+
+// the query into the pinned block and up: q at d_query_f64 and, for the prefilter, q^ right behind it (one copy)
+static int stage_query_f64(anrag_index *idx, hipStream_t st, const double *query, bool with_q32, double *w) {
+    double *h_query = reinterpret_cast<double *>(static_cast<char *>(idx->h_pinned) + kF64PinQuery);
+    const size_t dim = (size_t)idx->dim;
+    memcpy(h_query, query, dim * sizeof(double));
+    if (with_q32) *w = prefilter_f64_widening(query, reinterpret_cast<float *>(h_query + dim), idx->dim, idx->f64_pf_emax);
+    ANRAG_HIP(hipMemcpyAsync(idx->d_query_f64, h_query, dim * (sizeof(double) + (with_q32 ? sizeof(float) : 0)),
+                             hipMemcpyHostToDevice, st));
+    return ANRAG_OK;
+}
+
+// One fp64 query's dense lists on `st`, behind a settled pipeline, for the fp64 tail: the shadow scan and the threshold
+// kernel on list set 0 with q^, then the fp64 rescore -- or K1D.  The callers have made the list and query buffers.
+static int launch_dense_leg_f64(anrag_index *idx, hipStream_t st, const double *query, int32_t k, const uint32_t *d_allow) {
+    int rc;
+    if (!dense_f64_prefilter_applies(idx, k)) {
+        if ((rc = stage_query_f64(idx, st, query, false, nullptr))) return rc;
+        return launch_dense_scan_f64(idx, st, idx->d_query_f64, k, d_allow);
+    }
+    if ((rc = ensure_dense_prefilter_f64(idx, st))) return rc;
+    double w = 0.0;
+    if ((rc = stage_query_f64(idx, st, query, true, &w))) return rc;
+    const float *d_q32 = reinterpret_cast<const float *>(idx->d_query_f64 + idx->dim);
+    const int set = 0;
+    const uint32_t *allow = idx->d_dense_src ? d_allow : nullptr;
+    LaunchTimer t(idx, ANRAG_KERNEL_DENSE_SCAN, st);
+    const int64_t counted = idx->pf_queries;  // anrag_dense_prefilter_stats counts fp32 queries: this route has its own
+    rc = launch_dense_prefilter_scan(idx, st, &d_q32, 1, k, allow, &set);
+    idx->pf_queries = counted;
+    if (rc) return rc;
+    if ((rc = launch_dense_prefilter_threshold(idx, st, &d_q32, 1, k, &set))) return rc;
+    return launch_dense_prefilter_rescore_f64(idx, st, idx->d_query_f64, w, k);
+}
+
 #define ANRAG_ENTER(idx)                                                   \
     ANRAG_REQUIRE((idx) != nullptr, "index handle is NULL");              \
     std::lock_guard<std::mutex> lock__((idx)->mu);                        \
@@ -339,6 +402,7 @@ int anrag_index_create(int device, anrag_index **out) {
     idx->n_lanes = kScanLanesDefault;
     if (const char *env = getenv("ANRAG_SCAN_LANES")) { const int v = atoi(env); idx->n_lanes = v <= 0 ? 0 : (v >= 4 ? 4 : (v == 3 ? 2 : v)); }
     if (const char *env = getenv("ANRAG_DENSE_PREFILTER")) { const int v = atoi(env); idx->pf_mode = v < 0 ? -1 : (v > 2 ? 2 : v); }
+    if (const char *env = getenv("ANRAG_DENSE_F64_PREFILTER")) idx->f64_pf_on = atoi(env) != 0;
     for (int b = 0; b < kPipeSlots && e == hipSuccess; ++b) {
         e = hipEventCreateWithFlags(&idx->ev_scan[b], hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&idx->ev_bm25[b], hipEventDisableTiming);
@@ -364,6 +428,7 @@ static void free_dense(anrag_index *idx) {
     idx->pf_on = false;
     dev_free(idx, idx->d_dense_scores_f64, idx->n_rows);
     free_dense_f64_lists(idx);
+    idx->f64_pf_ready = false;
     dev_free(idx, idx->d_emb, idx->n_rows * idx->dim);
     dev_free(idx, idx->d_dense_src, idx->n_rows);
     dev_free(idx, idx->d_dense_doc, idx->n_rows);
@@ -578,14 +643,12 @@ int anrag_dense_search_f64(anrag_index *idx, const double *query, int32_t k, con
         idx->f64_sorted += 1;
         return dense_search_f64(idx, st, query, k, d_allow, out_doc, out_score, out_count);
     }
-    // K1D: per-wave fp64 lists, merged by the fp64 tail -- no score array, no sort (same ids, same score bits)
+    // K1D, or the shadow prefilter with K1D's rescoring: per-wave fp64 lists, merged by the fp64 tail -- no score array,
+    // no sort (same ids, same score bits)
     if ((rc = ensure_dense_f64_lists(idx)) || (rc = ensure_query_f64(idx))) return rc;
     char *pin = static_cast<char *>(idx->h_pinned);
-    double *h_query = reinterpret_cast<double *>(pin + kF64PinQuery);
     anrag_candidate *h_cand = reinterpret_cast<anrag_candidate *>(pin + kF64PinOut);
-    memcpy(h_query, query, (size_t)idx->dim * sizeof(double));
-    ANRAG_HIP(hipMemcpyAsync(idx->d_query_f64, h_query, (size_t)idx->dim * sizeof(double), hipMemcpyHostToDevice, st));
-    if ((rc = launch_dense_scan_f64(idx, st, idx->d_query_f64, k, d_allow))) return rc;
+    if ((rc = launch_dense_leg_f64(idx, st, query, k, d_allow))) return rc;
     if ((rc = launch_tail_f64(idx, st, /*dense*/ true, /*bm25*/ false, k, kTailCandidates, 0, 0, 0, 0, idx->d_cand_out, nullptr)))
         return rc;
     ANRAG_HIP(hipMemcpyAsync(h_cand, idx->d_cand_out, (size_t)k * sizeof(anrag_candidate), hipMemcpyDeviceToHost, st));
@@ -606,6 +669,24 @@ int anrag_dense_f64_stats(anrag_index *idx, int64_t *scanned, int64_t *sorted) {
     ANRAG_ENTER(idx);
     if (scanned) *scanned = idx->f64_scanned;
     if (sorted) *sorted = idx->f64_sorted;
+    return ANRAG_OK;
+}
+
+int anrag_set_dense_f64_prefilter(anrag_index *idx, int32_t on) {
+    ANRAG_ENTER(idx);
+    ANRAG_REQUIRE(on == 0 || on == 1, "on must be 0 (K1D for every fp64 query) or 1 (the shadow prefilter while a form is built)");
+    idx->f64_pf_on = on == 1;
+    return ANRAG_OK;
+}
+
+int anrag_dense_f64_prefilter_stats(anrag_index *idx, int64_t *queries, int64_t *survivors) {
+    ANRAG_ENTER(idx);
+    int rc = sync_all(idx);
+    if (rc) return rc;
+    int64_t s = 0;
+    if ((rc = dense_prefilter_f64_survivors(idx, &s))) return rc;
+    if (queries) *queries = idx->f64_pf_ready ? idx->f64_pf_queries : 0;
+    if (survivors) *survivors = s;
     return ANRAG_OK;
 }
 
@@ -1342,15 +1423,11 @@ int anrag_hybrid_search_f64(anrag_index *idx, const double *query, const int32_t
     if ((rc = stage_allow(st, allow_dense, n_dense_sources, reinterpret_cast<uint32_t *>(pin), idx->d_allow_a, &d_ad))) return rc;
     if ((rc = stage_allow(st, allow_bm25, n_bm25_sources, reinterpret_cast<uint32_t *>(pin) + kAllowWords, idx->d_allow_b, &d_ab)))
         return rc;
-    if (use_dense) {
-        memcpy(pin + kF64PinQuery, query, (size_t)idx->dim * sizeof(double));
-        ANRAG_HIP(hipMemcpyAsync(idx->d_query_f64, pin + kF64PinQuery, (size_t)idx->dim * sizeof(double), hipMemcpyHostToDevice, st));
-    }
     if (use_bm25) {
         memcpy(pin + kF64PinTerms, term_ids, (size_t)n_terms * sizeof(int32_t));
         ANRAG_HIP(hipMemcpyAsync(idx->d_terms, pin + kF64PinTerms, (size_t)n_terms * sizeof(int32_t), hipMemcpyHostToDevice, st));
     }
-    if (use_dense && (rc = launch_dense_scan_f64(idx, st, idx->d_query_f64, similarity_k, d_ad))) return rc;
+    if (use_dense && (rc = launch_dense_leg_f64(idx, st, query, similarity_k, d_ad))) return rc;
     if (use_bm25 && (rc = launch_bm25_lists(idx, st, idx->d_terms, n_terms, similarity_k, d_ab, nullptr, 0))) return rc;
     int32_t *d_count = dense_f64_count(idx);
     if ((rc = launch_tail_f64(idx, st, use_dense, use_bm25, similarity_k, kTailFuse, w_dense, w_bm25, wrrf_k, top_n,
@@ -1618,6 +1695,25 @@ int anrag_debug_prefilter_read(anrag_index *idx, int32_t *out_form, int64_t *out
     if (out_meta)
         ANRAG_HIP(hipMemcpy(out_meta, idx->d_pf_m, n * (form == kPrefilterInt8 ? 4 : 1) * sizeof(float),
                             hipMemcpyDeviceToHost));
+    return ANRAG_OK;
+}
+
+int anrag_debug_prefilter_f64(anrag_index *idx, const double *query, float *out_q32, double *out_w, double *out_emax) {
+    ANRAG_ENTER(idx);
+    ANRAG_REQUIRE(idx->d_emb != nullptr && idx->pf_on, "the dense prefilter is off");
+    ANRAG_REQUIRE(dense_scan_f64_serves(idx), "the fp64 list scan does not serve dim %d", idx->dim);
+    ANRAG_REQUIRE(query && out_q32 && out_w && out_emax, "NULL operand");
+    int rc = sync_all(idx);
+    if (rc) return rc;
+    if ((rc = ensure_dense_f64_lists(idx)) || (rc = ensure_query_f64(idx))) return rc;
+    hipStream_t st = idx->primary;
+    if ((rc = ensure_dense_prefilter_f64(idx, st))) return rc;
+    double w = 0.0;
+    if ((rc = stage_query_f64(idx, st, query, true, &w))) return rc;  // ... and back from where the scan reads it
+    ANRAG_HIP(hipMemcpyAsync(out_q32, idx->d_query_f64 + idx->dim, (size_t)idx->dim * sizeof(float), hipMemcpyDeviceToHost, st));
+    ANRAG_HIP(hipStreamSynchronize(st));
+    *out_w = w;
+    *out_emax = idx->f64_pf_emax;
     return ANRAG_OK;
 }
 

@@ -224,6 +224,11 @@ struct anrag_index {
     double *d_blk_score_f64q = nullptr;    // fp64-query list scan (K1D, dense_scan_f64.hip): ONE set [kMaxScanLists][kListLen]
     bool f64_scan_on = true;               // anrag_set_dense_f64_scan
     int64_t f64_scanned = 0, f64_sorted = 0;  // fp64 queries answered by K1D / by the score array + sort
+    // the shadow prefilter for fp64 queries (K1FD, dense_prefilter_f64.hip): on while a prefilter form is built
+    bool f64_pf_on = true;                 // anrag_set_dense_f64_prefilter
+    bool f64_pf_ready = false;             // Emax computed for the loaded corpus (the first such query after a load)
+    double f64_pf_emax = 0.0;              // largest finite row norm <= 2^60, rounded up
+    int64_t f64_pf_queries = 0;            // fp64 queries answered through the prefilter since then
     void *d_sort_tmp = nullptr;
     int64_t sort_tmp_bytes = 0;
     void *d_sort_buf = nullptr;
@@ -409,6 +414,12 @@ void free_dense_f64_lists(anrag_index *idx);
 int32_t *dense_f64_count(const anrag_index *idx);  // a device int32 behind the lists: the fused call's count
 int ensure_query_f64(anrag_index *idx);
 int launch_dense_scan_f64(anrag_index *idx, hipStream_t st, const double *d_query, int32_t k, const uint32_t *d_allow_bits);
+// K1FD, the shadow prefilter for one fp64 query (dense_prefilter_f64.hip): behind launch_dense_prefilter_scan and
+// launch_dense_prefilter_threshold on list set 0 with fl32(query), the survivors (hi >= T - 2w) rescored with K1D's
+// arithmetic into K1D's lists.  ensure_...: Emax of the corpus (idx->f64_pf_emax), once per dense load, syncs `st`.
+int ensure_dense_prefilter_f64(anrag_index *idx, hipStream_t st);
+int launch_dense_prefilter_rescore_f64(anrag_index *idx, hipStream_t st, const double *d_query, double w, int32_t k);
+int dense_prefilter_f64_survivors(anrag_index *idx, int64_t *out);  // cumulative rows rescored since Emax was computed
 // K2: up to 256 queries per pass on the fp32 matrix cores (dense_batched.hip)
 bool batched_path_applies(const anrag_index *idx, int32_t n_queries, int32_t k);
 int launch_dense_batched(anrag_index *idx, hipStream_t st, const float *d_queries, int32_t nq, int32_t k,

@@ -487,6 +487,18 @@ class Index:
         nat.check(self._lib.anrag_dense_f64_stats(self.handle, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def set_dense_f64_prefilter(self, on: bool = True) -> None:
+        """Route of the float64 dense leg while a prefilter form is built: the shadow prefilter with fp64 rescoring
+        (default), or the list scan K1D (`anrag_set_dense_f64_prefilter`).  Same ids and score bits on both."""
+        nat.check(self._lib.anrag_set_dense_f64_prefilter(self.handle, 1 if on else 0))
+
+    def dense_f64_prefilter_stats(self) -> tuple:
+        """(float64 queries answered through the prefilter, rows rescored for them) since the first such query after
+        the last dense load."""
+        q, s = C.c_int64(0), C.c_int64(0)
+        nat.check(self._lib.anrag_dense_f64_prefilter_stats(self.handle, C.byref(q), C.byref(s)))
+        return q.value, s.value
+
     def set_batched_precision(self, mode: str = "f32") -> None:
         """"f32": exact f32 MFMA (default).  "bf16x3": split-precision products on the bf16 matrix cores (scores within
         ~3e-5 of f32 for unit-norm vectors)."""
@@ -532,6 +544,16 @@ class Index:
         nat.check(self._lib.anrag_debug_prefilter_bounds(self.handle, q.ctypes.data, q.shape[0], int(k), nat.ptr(allow), ns,
                                                          self.PREFILTER_SENTINEL, hi.ctypes.data, thr.ctypes.data))
         return hi, thr
+
+    def debug_prefilter_f64(self, query):
+        """What the float64 prefilter route derives from `query` (`anrag_debug_prefilter_f64`)
+        -> (q32 [dim] float32 as staged for the shadow scan, w, Emax)."""
+        q = np.ascontiguousarray(query, dtype=np.float64).reshape(-1)
+        assert q.size == self.dim, f"query dim {q.size} != index dim {self.dim}"
+        q32 = np.empty(self.dim, np.float32)
+        w, emax = C.c_double(0.0), C.c_double(0.0)
+        nat.check(self._lib.anrag_debug_prefilter_f64(self.handle, q.ctypes.data, q32.ctypes.data, C.byref(w), C.byref(emax)))
+        return q32, w.value, emax.value
 
     LIST_ROW_SENTINEL = 0xFFFFFFFE  # never a row (a shard holds at most 2^32 - 2), nor the empty slot's 0xFFFFFFFF
 

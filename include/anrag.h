@@ -165,7 +165,13 @@ int anrag_dense_search(anrag_index *idx, const float *queries, int32_t n_queries
  * the Python shim calls this one when it is handed a float64 query.)
  * k <= ANRAG_FUSED_K_MAX and dim % 4 == 0, dim <= 3072: a streaming scan that keeps per-wave fp64 lists (K1D) and
  * the list merge answer instead -- no score array, no sort; the same ids and the same score BITS (one summation order
- * in both kernels).  Its list buffer (512 KB) is allocated by the first such query. */
+ * in both kernels).  Its list buffer (512 KB) is allocated by the first such query.
+ * While a form of the dense prefilter is built (anrag_set_dense_prefilter) and the list scan serves, the query goes
+ * through the shadow prefilter instead of K1D (anrag_set_dense_f64_prefilter): the shadow scan and the threshold kernel
+ * run with the query rounded to fp32, the rows whose upper bound reaches the threshold less twice a per-query widening
+ * w are rescored with K1D's arithmetic, and the same list merge answers -- the same ids and score bits again, from a
+ * quarter (int8) or half (fp16) of the bytes.  The first such query after a dense load also computes the corpus's
+ * largest row norm (one extra kernel and host wait). */
 int anrag_dense_search_f64(anrag_index *idx, const double *query, int32_t k,
                            const uint8_t *allow_source, int32_t n_sources, int64_t *out_doc,
                            double *out_score, int32_t *out_count);
@@ -177,8 +183,19 @@ int anrag_dense_search_f64(anrag_index *idx, const double *query, int32_t k,
 int anrag_set_dense_f64_scan(anrag_index *idx, int32_t on);
 
 /* Cumulative fp64 queries answered by the list scan (anrag_hybrid_search_f64's dense legs included) and by the score
- * array + sort. */
+ * array + sort.  `scanned` counts every fp64 query answered from per-wave lists: K1D's and the shadow prefilter's. */
 int anrag_dense_f64_stats(anrag_index *idx, int64_t *scanned, int64_t *sorted);
+
+/* Route of the fp64 dense leg (anrag_dense_search_f64 with k <= ANRAG_FUSED_K_MAX, anrag_hybrid_search_f64) while a
+ * prefilter form is built and the list scan is on and serves the dimension: 1 (default) the shadow prefilter with
+ * K1D's rescoring, 0 K1D.  Without a built form it has no effect.  The answers never depend on it.  The environment
+ * variable ANRAG_DENSE_F64_PREFILTER=0|1, read at anrag_index_create, sets the initial value. */
+int anrag_set_dense_f64_prefilter(anrag_index *idx, int32_t on);
+
+/* Cumulative counters of the fp64 prefilter route since the first such query after the last anrag_dense_load: queries
+ * it answered and rows it rescored (waits for the index's streams).  Separate from anrag_dense_prefilter_stats, which
+ * counts fp32 queries only. */
+int anrag_dense_f64_prefilter_stats(anrag_index *idx, int64_t *queries, int64_t *survivors);
 
 /* Same, all operands in HBM, no host sync: d_out is n_queries x k anrag_candidate.
  * n_queries > 1: up to 8 queries share a scan launch (each is still its own pass over the matrix; a workgroup starts
@@ -506,6 +523,12 @@ int anrag_debug_prefilter_read(anrag_index *idx, int32_t *out_form, int64_t *out
 int anrag_debug_prefilter_bounds(anrag_index *idx, const float *queries, int32_t n_queries, int32_t k,
                                  const uint8_t *allow_source, int32_t n_sources, uint32_t sentinel, float *out_hi,
                                  float *out_threshold);
+/* What the fp64 prefilter route derives from one float64 query, exactly as anrag_dense_search_f64 computes it, for
+ * tests of the widened bound (tests/test_gpu_dense_prefilter_f64.py): out_q32 host [dim], the fp32 query the shadow
+ * scan reads (read back from the device); out_w, the widening w = (||q - q32|| + gamma64 ||q||) Emax + dim 2^-1000
+ * rounded upward; out_emax, the largest row norm over rows whose norm is finite and <= 2^60, rounded upward.  Needs a
+ * built prefilter form.  Waits for the index's streams; after the first call it does not allocate. */
+int anrag_debug_prefilter_f64(anrag_index *idx, const double *query, float *out_q32, double *out_w, double *out_emax);
 /* The per-wave lists of the dense top-k seen from outside, for tests of the lists and of their merges
  * (tests/test_gpu_dense_lists.py).  Runs the list-producing half of a scan group of 1..16 queries exactly as the product
  * runs it (list sets 0 .. n_queries - 1, the primary stream, no deferred merge riding along): the fp32 scan with the
