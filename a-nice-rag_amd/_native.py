@@ -114,6 +114,10 @@ _SIGNATURES = {
     "anrag_debug_dense_lists": [_p, _p, _i32, _i32, _p, _i32, C.c_uint32, C.c_uint32, C.POINTER(_i32), _p, _p],
     "anrag_rank_batch": [_p, _i32, _i32, _i32, _f64, _i32, _i64, _p, _p, _p, _p, _p],
     "anrag_rank_caps": [C.POINTER(_i32), C.POINTER(_i32)],
+    "anrag_set_rank_wide": [_i32],
+    "anrag_rank_wide_stats": [C.POINTER(_i64), C.POINTER(_i64)],
+    "anrag_rank_wide_gate": [_i32, _i32, _i32, C.POINTER(_i32)],
+    "anrag_debug_rank_select": [_p, _p, _i32, _p, _i32, _i64, _i32, _i32, _p, _i32, _i32, _p, _p, _p],
     "anrag_shard_group_create": [_p, _i32, C.POINTER(_p)],
     "anrag_shard_group_destroy": [_p],
     "anrag_shard_group_dense_load": [_p, _p, _i64, _i32, _p, _p, _i64],

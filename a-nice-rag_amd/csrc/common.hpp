@@ -466,10 +466,22 @@ int reserve_call_pool(anrag_index *idx, int64_t bytes, char **out);
 
 // ---- full ranking (rank_batch.hip): the pieces anrag_rank_batch and anrag_shard_group_rank_batch share
 int rank_list_cap(bool fp64);  // anrag_rank_caps
-// one workgroup per segment: the k best of n scores by (score desc, position asc) -> rows, keys (fp64, nullable), counts
+// The wide form of the select (rank_batch.hip, "K4 wide") needs scratch of the caller's rank_pool: rank_wide_bytes for
+// the launch's segments, asked for where rank_wide_wanted says the current mode would take it.
+struct RankWide {
+    char *scratch = nullptr;
+    int64_t bytes = 0;
+    int32_t form = -1;   // -1: by anrag_set_rank_wide; 0 narrow; 1 wide wherever n > the list cap (anrag_debug_rank_select)
+    int32_t parts = 0;   // 0: the launcher chooses the slices
+};
+bool rank_wide_wanted(bool fp64, int32_t n_seg, int32_t n);
+bool rank_wide_gate(bool fp64, int32_t n_seg, int32_t n);  // the auto gate alone
+int64_t rank_wide_bytes(bool fp64, int32_t n_seg);
+// the k best of n scores per segment by (score desc, position asc) -> rows, keys (fp64, nullable), counts: one workgroup
+// per segment, or (wide) a segment across the device
 int launch_rank_sort(int device, hipStream_t st, int32_t n_seg, const void *keys, bool fp64, int64_t key_stride, int32_t n,
                      int32_t k, const int32_t *seg_k, uint32_t *out_rows, double *out_keys, int64_t out_stride,
-                     int32_t *out_count);
+                     int32_t *out_count, const RankWide &wide = RankWide());
 // every map inside [0, id_space) and injective (a NULL map: the leg's rows fit the id space)
 int rank_check_maps(int32_t n_legs, const int64_t *const *maps, const int64_t *leg_rows, int64_t id_space);
 struct RankTailLeg {
@@ -499,6 +511,7 @@ struct RankTail {
     int32_t *d_out_cnt = nullptr;
     int64_t *d_expect = nullptr;
     int32_t *d_rank = nullptr;
+    RankWide wide;                             // for the fused-sums select (fusion in HBM)
 };
 void rank_fuse_table(const RankTail &t, uint64_t *tab);  // 6 * ANRAG_WRRF_MAX_LISTS words
 int launch_rank_tail(const RankTail &t, int32_t c, bool want_ids);

@@ -21,8 +21,10 @@
 //      instead of sorts wherever a list is not needed (rank_count_kernel; the count in rank_fuse_sort_kernel).
 // HBM- / issue-bound score tiles, LDS-bound sorts.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <vector>
 
 #include "common.hpp"
@@ -267,6 +269,71 @@ __device__ __forceinline__ void lds_bitonic_sort(uint32_t *arr, int32_t m) {
     }
 }
 
+// One element of a select pass into the LDS histogram.  Heavy ties (a million zero BM25 scores) put a whole wave into
+// one bin: one add instead of 64 serialised ones.
+__device__ __forceinline__ void hist_add(uint32_t *hist, bool cand, uint32_t bin, int lane) {
+    const unsigned long long m = __ballot(cand);
+    if (m) {
+        const int leader = __builtin_ctzll(m);
+        const uint32_t b0 = read_lane(bin, leader);
+        if (__ballot(cand && bin == b0) == m) {
+            if (lane == leader) atomicAdd(&hist[b0], (uint32_t)__builtin_popcountll(m));
+        } else if (cand) {
+            atomicAdd(&hist[bin], 1u);
+        }
+    }
+}
+
+// ONE wave: the bin of the nb-bin LDS histogram that holds the want-th best candidate of the current prefix, lane l
+// looking after bins [l * per, (l+1) * per).  first: the pass over the whole segment, want = min(kq, candidates).
+// ctrl[1] = candidates of the prefix, ctrl[2] = the bin, ctrl[3] = candidates in the bins above it, ctrl[4] = in it.
+__device__ __forceinline__ void pick_bin(const uint32_t *hist, int nb, bool first, int32_t kq, int32_t k_rem, int lane,
+                                         uint32_t *ctrl) {
+    const int per = nb / kWave;
+    uint32_t s = 0;
+    for (int b = 0; b < per; ++b) s += hist[lane * per + b];
+    uint32_t x = s;  // inclusive suffix sum over the lanes
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const uint32_t y = __shfl_down(x, off, kWave);
+        if (lane + off < kWave) x += y;
+    }
+    const uint32_t total = read_lane(x, 0);
+    int32_t want = k_rem;
+    if (first) want = (uint32_t)kq < total ? kq : (int32_t)total;  // = k_eff
+    if (lane == 0) ctrl[1] = total;
+    const uint32_t upper = x - s;  // candidates in the bins of higher lanes
+    if (want > 0 && upper < (uint32_t)want && (uint32_t)want <= upper + s) {
+        uint32_t acc = upper;
+        for (int b = per - 1; b >= 0; --b) {
+            const uint32_t h = hist[lane * per + b];
+            if (acc + h >= (uint32_t)want) {
+                ctrl[2] = (uint32_t)(lane * per + b);
+                ctrl[3] = acc;
+                ctrl[4] = h;
+                break;
+            }
+            acc += h;
+        }
+    }
+}
+
+// The sorted survivors in LDS -> the segment's rows, keys and count.  All threads of the workgroup.
+template <int W, int CAP>
+__device__ __forceinline__ void emit_sorted(const uint32_t *arr, int64_t seg, int32_t k_eff, uint32_t *__restrict__ out_tie,
+                                            double *__restrict__ out_key, int64_t out_stride,
+                                            int32_t *__restrict__ out_count) {
+    const int tid = threadIdx.x;
+    for (int32_t i = tid; i < k_eff; i += kRankThreads) {
+        out_tie[seg * out_stride + i] = ~arr[i];
+        if (out_key) {
+            if constexpr (W == 2) out_key[seg * out_stride + i] = (double)unorder_bits(arr[CAP + i]);
+            else out_key[seg * out_stride + i] = unorder_bits(((uint64_t)arr[2 * CAP + i] << 32) | arr[CAP + i]);
+        }
+    }
+    if (tid == 0) out_count[seg] = k_eff;
+}
+
 // ------------------------------------------------------------------ select + sort, one workgroup per segment
 // keys + seg * key_stride: n scores of the segment (a key of -inf = "not a candidate": a filtered row, a document no
 // list names).  TIE: ties + seg * tie_stride holds each element's tie-break word (ascending; unique inside a segment),
@@ -335,49 +402,10 @@ __global__ __launch_bounds__(kRankThreads) void seg_topk_sort_kernel(
                 const Comp<W> c = make_comp(key, tie);
                 const bool cand = key != neg_inf<KEY>() && comp_match(c, thr, pbits);
                 const uint32_t bin = comp_bits(c, lo, len);
-                const unsigned long long m = __ballot(cand);
-                if (m) {
-                    // heavy ties (a million zero BM25 scores) put a whole wave into one bin: one add instead of 64
-                    // serialised ones
-                    const int leader = __builtin_ctzll(m);
-                    const uint32_t b0 = read_lane(bin, leader);
-                    if (__ballot(cand && bin == b0) == m) {
-                        if (lane == leader) atomicAdd(&hist[b0], (uint32_t)__builtin_popcountll(m));
-                    } else if (cand) {
-                        atomicAdd(&hist[bin], 1u);
-                    }
-                }
+                hist_add(hist, cand, bin, lane);
             });
             __syncthreads();
-            if (wave == 0) {  // the bin that holds the k_rem-th best: lane l looks after bins [l * per, (l+1) * per)
-                const int per = nb / kWave;
-                uint32_t s = 0;
-                for (int b = 0; b < per; ++b) s += hist[lane * per + b];
-                uint32_t x = s;  // inclusive suffix sum over the lanes
-#pragma unroll
-                for (int off = 1; off < kWave; off <<= 1) {
-                    const uint32_t y = __shfl_down(x, off, kWave);
-                    if (lane + off < kWave) x += y;
-                }
-                const uint32_t total = read_lane(x, 0);
-                int32_t want = k_rem;
-                if (pbits == 0) want = (uint32_t)kq < total ? kq : (int32_t)total;  // = k_eff
-                if (lane == 0) ctrl[1] = total;
-                const uint32_t upper = x - s;  // candidates in the bins of higher lanes
-                if (want > 0 && upper < (uint32_t)want && (uint32_t)want <= upper + s) {
-                    uint32_t acc = upper;
-                    for (int b = per - 1; b >= 0; --b) {
-                        const uint32_t h = hist[lane * per + b];
-                        if (acc + h >= (uint32_t)want) {
-                            ctrl[2] = (uint32_t)(lane * per + b);
-                            ctrl[3] = acc;
-                            ctrl[4] = h;
-                            break;
-                        }
-                        acc += h;
-                    }
-                }
-            }
+            if (wave == 0) pick_bin(hist, nb, pbits == 0, kq, k_rem, lane, ctrl);
             __syncthreads();
             if (pbits == 0) {
                 const uint32_t total = ctrl[1];
@@ -422,14 +450,7 @@ __global__ __launch_bounds__(kRankThreads) void seg_topk_sort_kernel(
 
     lds_bitonic_sort<W, CAP>(arr, m);
 
-    for (int32_t i = tid; i < k_eff; i += T) {
-        out_tie[seg * out_stride + i] = ~arr[i];
-        if (out_key) {
-            if constexpr (W == 2) out_key[seg * out_stride + i] = (double)unorder_bits(arr[CAP + i]);
-            else out_key[seg * out_stride + i] = unorder_bits(((uint64_t)arr[2 * CAP + i] << 32) | arr[CAP + i]);
-        }
-    }
-    if (tid == 0) out_count[seg] = k_eff;
+    emit_sorted<W, CAP>(arr, seg, k_eff, out_tie, out_key, out_stride, out_count);
 }
 
 // ------------------------------------------------------------------ segments that fit the LDS: stable LSD radix sort
@@ -877,12 +898,372 @@ __global__ __launch_bounds__(kRankThreads) void rank_fuse_sort_kernel(const uint
     if (tid == 0) out_cnt[qe] = k_out;
 }
 
+// ------------------------------------------------------------------ K4 wide: one segment across the device
+// The select + sort above gives a segment to ONE workgroup: right for lists of queries (a segment per CU), wrong for one
+// query at a million rows, where one CU makes every pass over 4-8 MB while the others idle.  The wide form cuts a segment
+// into P contiguous slices, grid (P, n_seg), and splits the kernel at the points where the narrow form has a barrier
+// over the whole segment:
+//   pass kernel (one launch per digit):  LDS histogram of the slice -> integer atomicAdd of its non-zero bins into the
+//       segment's histogram in HBM -> a ticket; the workgroup that draws the LAST ticket does wave 0's pick above, writes
+//       the segment's control record, clears the OTHER histogram (two, alternating) and resets the ticket.  Nobody waits
+//       for anybody; only integer atomics touch shared words, so the record does not depend on arrival order.
+//   compaction kernel:  candidates not below thr -> the segment's survivor buffer in HBM (<= CAP composites, any order).
+//   finish kernel (one workgroup per segment):  survivors -> LDS, lds_bitonic_sort, emit_sorted.
+// The host cannot know how many digits a segment needs and never syncs in between: it enqueues the worst case,
+// ceil(B / 11) pass launches (6 for fp32 composites, 9 for fp64); a workgroup whose segment is done returns after one
+// load of the record.  Same composites, same thr, same survivors as the narrow form, hence the same output bits.
+constexpr int kWideMinSlice = 4096;  // elements: below this a slice's fixed costs (histogram clear, flush, ticket) dominate
+constexpr int kWideCtrlWords = 16;   // control record of a segment, 64 bytes
+enum : int {
+    kWcThr0 = 0,  // prefix, composite words w0 / key lo (fp32: key) / key hi
+    kWcThr1,
+    kWcThr2,
+    kWcPbits,   // bits of the prefix that are settled
+    kWcAbove,   // candidates above the prefix's range
+    kWcKrem,    // rank wanted inside the range
+    kWcKeff,    // min(k, candidates)
+    kWcDone,    // 0 selecting, 1 thr is final, 2 nothing to emit
+    kWcTicket,  // workgroups of the current pass that have flushed
+    kWcSurv,    // survivors written by the compaction
+};
+constexpr int kWideBins = 1 << kRankDigitBits;
+template <int W>
+constexpr int wide_passes() { return (32 * W + kRankDigitBits - 1) / kRankDigitBits; }
+
+// bytes of scratch for n_seg segments: [records][histogram 0][histogram 1][survivors]; the first two are zeroed per call
+template <int W>
+constexpr int64_t wide_zero_bytes(int64_t n_seg) { return n_seg * (kWideCtrlWords + kWideBins) * 4; }
+template <int W>
+constexpr int64_t wide_scratch_bytes(int64_t n_seg) {
+    return n_seg * ((int64_t)(kWideCtrlWords + 2 * kWideBins) * 4 + (int64_t)W * rank_cap<W>() * 4) + 256;
+}
+struct WideScratch {
+    uint32_t *ctrl, *hist, *surv;  // hist: [2][n_seg][kWideBins]; surv: [n_seg][W][CAP]
+};
+
+__device__ __forceinline__ Comp<2> wide_thr(const uint32_t *c, Comp<2> *) { return Comp<2>{c[kWcThr0], c[kWcThr1]}; }
+__device__ __forceinline__ Comp<3> wide_thr(const uint32_t *c, Comp<3> *) {
+    return Comp<3>{c[kWcThr0], ((uint64_t)c[kWcThr2] << 32) | c[kWcThr1]};
+}
+__device__ __forceinline__ void wide_put_thr(uint32_t *c, const Comp<2> &t) {
+    c[kWcThr0] = t.w0;
+    c[kWcThr1] = t.w1;
+}
+__device__ __forceinline__ void wide_put_thr(uint32_t *c, const Comp<3> &t) {
+    c[kWcThr0] = t.w0;
+    c[kWcThr1] = (uint32_t)t.k;
+    c[kWcThr2] = (uint32_t)(t.k >> 32);
+}
+
+// f(key, tie word, in range) for elements [s0, s1) of a segment, kRankLoads independent loads per thread in flight
+template <typename KEY, bool TIE, class F>
+__device__ __forceinline__ void wide_for_each(const KEY *__restrict__ kp, const uint32_t *__restrict__ tp, int32_t s0,
+                                              int32_t s1, F &&f) {
+    constexpr int T = kRankThreads;
+    const int tid = threadIdx.x;
+    for (int32_t base = s0; base < s1; base += T * kRankLoads) {
+        KEY kv[kRankLoads];
+        uint32_t tv[kRankLoads];
+#pragma unroll
+        for (int u = 0; u < kRankLoads; ++u) {
+            const int32_t i = base + u * T + tid;
+            kv[u] = i < s1 ? kp[i] : neg_inf<KEY>();
+            tv[u] = (uint32_t)i;
+            if constexpr (TIE) tv[u] = i < s1 ? tp[i] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < kRankLoads; ++u) f(kv[u], tv[u]);
+    }
+}
+
+template <typename KEY, bool TIE>
+__global__ __launch_bounds__(kRankThreads) void seg_wide_pass_kernel(
+    const KEY *__restrict__ keys, int64_t key_stride, const uint32_t *__restrict__ ties, int64_t tie_stride, int32_t n,
+    int32_t slice, int32_t k, const int32_t *__restrict__ seg_k, int32_t pass, uint32_t *ctrl_all, uint32_t *hist_all) {
+    constexpr int W = sizeof(KEY) == 4 ? 2 : 3;
+    constexpr int B = 32 * W;
+    constexpr int CAP = rank_cap<W>();
+    constexpr int T = kRankThreads;
+    __shared__ __attribute__((aligned(16))) uint32_t hist[kWideBins];
+    __shared__ __attribute__((aligned(16))) uint32_t lctrl[8];  // [1..4] pick_bin's words, [5] "this workgroup drew the last ticket"
+
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+    const int64_t seg = blockIdx.y, n_seg = gridDim.y;
+    int32_t kq = k;
+    if (seg_k) kq = seg_k[seg] < k ? seg_k[seg] : k;
+    if (kq <= 0) return;
+    uint32_t *c = ctrl_all + seg * kWideCtrlWords;
+    if (c[kWcDone] != 0u) return;
+    const Comp<W> thr = wide_thr(c, (Comp<W> *)nullptr);
+    const int pbits = (int)c[kWcPbits];
+    const uint32_t above = c[kWcAbove];
+    const int32_t k_rem = (int32_t)c[kWcKrem];
+    uint32_t *gh = hist_all + ((int64_t)(pass & 1) * n_seg + seg) * kWideBins;
+    uint32_t *gh_next = hist_all + ((int64_t)((pass + 1) & 1) * n_seg + seg) * kWideBins;
+
+    const int len = B - pbits < kRankDigitBits ? B - pbits : kRankDigitBits;
+    const int lo = B - pbits - len;
+    const int nb = 1 << len;
+    for (int i = tid; i < kWideBins; i += T) hist[i] = 0;
+    __syncthreads();
+    const int32_t s0 = (int32_t)blockIdx.x * slice;  // (< n: the launcher's P = ceil(n / slice))
+    const int32_t s1 = n - s0 < slice ? n : s0 + slice;
+    wide_for_each<KEY, TIE>(keys + seg * key_stride, TIE ? ties + seg * tie_stride : nullptr, s0, s1,
+                            [&](KEY key, uint32_t tie) __attribute__((always_inline)) {
+                                const Comp<W> cm = make_comp(key, tie);
+                                const bool cand = key != neg_inf<KEY>() && comp_match(cm, thr, pbits);
+                                hist_add(hist, cand, comp_bits(cm, lo, len), lane);
+                            });
+    __syncthreads();
+    for (int i = tid; i < nb; i += T) {
+        const uint32_t h = hist[i];
+        if (h) atomicAdd(&gh[i], h);
+    }
+    // every wave's adds have left before the ticket is drawn; the last drawer reads the sums past its L1
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        __threadfence();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const uint32_t t = atomicAdd(&c[kWcTicket], 1u);
+        lctrl[5] = t == gridDim.x - 1 ? 1u : 0u;
+    }
+    __syncthreads();
+    if (lctrl[5] == 0u) return;
+    __threadfence();
+    for (int i = tid; i < kWideBins; i += T) {
+        hist[i] = i < nb ? __hip_atomic_load(&gh[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+        gh_next[i] = 0u;
+    }
+    __syncthreads();
+    if (wave == 0) pick_bin(hist, nb, pbits == 0, kq, k_rem, lane, lctrl);
+    __syncthreads();
+    if (tid == 0) {
+        int32_t kr = k_rem;
+        bool nothing = false;
+        if (pbits == 0) {
+            const uint32_t total = lctrl[1];
+            const int32_t k_eff = (uint32_t)kq < total ? kq : (int32_t)total;
+            c[kWcKeff] = (uint32_t)k_eff;
+            kr = k_eff;
+            nothing = k_eff == 0;
+        }
+        if (nothing) {
+            c[kWcDone] = 2u;
+        } else {
+            const uint32_t bin = lctrl[2], acc = lctrl[3], inbin = lctrl[4];
+            wide_put_thr(c, comp_or_bits(thr, bin, lo));
+            c[kWcPbits] = (uint32_t)(pbits + len);
+            c[kWcAbove] = above + acc;
+            c[kWcKrem] = (uint32_t)(kr - (int32_t)acc);
+            c[kWcDone] = (above + acc + inbin <= (uint32_t)CAP || pbits + len == B) ? 1u : 0u;
+        }
+        atomicExch(&c[kWcTicket], 0u);
+    }
+}
+
+// candidates not below thr -> surv (word w of survivor i at surv[w * CAP + i]).  Positions: per step of the slice the
+// waves take theirs from an LDS counter (one add per ballot), the workgroup takes its base from the segment's counter
+// with ONE add -- a few hundred adds on that word per segment instead of one per surviving wave ballot.
+template <typename KEY, bool TIE>
+__global__ __launch_bounds__(kRankThreads) void seg_wide_compact_kernel(
+    const KEY *__restrict__ keys, int64_t key_stride, const uint32_t *__restrict__ ties, int64_t tie_stride, int32_t n,
+    int32_t slice, int32_t k, const int32_t *__restrict__ seg_k, uint32_t *ctrl_all, uint32_t *surv_all) {
+    constexpr int W = sizeof(KEY) == 4 ? 2 : 3;
+    constexpr int CAP = rank_cap<W>();
+    constexpr int T = kRankThreads;
+    __shared__ uint32_t lctrl[2];  // [0] survivors of this step  [1] their base in the segment's buffer
+    const int tid = threadIdx.x, lane = tid & (kWave - 1);
+    const int64_t seg = blockIdx.y;
+    int32_t kq = k;
+    if (seg_k) kq = seg_k[seg] < k ? seg_k[seg] : k;
+    if (kq <= 0) return;
+    uint32_t *c = ctrl_all + seg * kWideCtrlWords;
+    if (c[kWcDone] == 2u) return;
+    const Comp<W> thr = wide_thr(c, (Comp<W> *)nullptr);
+    uint32_t *surv = surv_all + seg * (int64_t)(W * CAP);
+    const KEY *__restrict__ kp = keys + seg * key_stride;
+    const uint32_t *__restrict__ tp = TIE ? ties + seg * tie_stride : nullptr;
+    const int32_t s0 = (int32_t)blockIdx.x * slice;
+    const int32_t s1 = n - s0 < slice ? n : s0 + slice;
+    for (int32_t base = s0; base < s1; base += T * kRankLoads) {
+        if (tid == 0) lctrl[0] = 0;
+        __syncthreads();
+        KEY kv[kRankLoads];
+        uint32_t tv[kRankLoads];
+#pragma unroll
+        for (int u = 0; u < kRankLoads; ++u) {
+            const int32_t i = base + u * T + tid;
+            kv[u] = i < s1 ? kp[i] : neg_inf<KEY>();
+            tv[u] = (uint32_t)i;
+            if constexpr (TIE) tv[u] = i < s1 ? tp[i] : 0u;
+        }
+        uint32_t pos[kRankLoads];  // position inside the step, ~0u: not kept
+#pragma unroll
+        for (int u = 0; u < kRankLoads; ++u) {
+            const bool keep = kv[u] != neg_inf<KEY>() && !comp_gt(thr, make_comp(kv[u], tv[u]));
+            const unsigned long long m = __ballot(keep);
+            pos[u] = 0xFFFFFFFFu;
+            if (m) {
+                uint32_t b = 0;
+                if (lane == 0) b = atomicAdd(&lctrl[0], (uint32_t)__builtin_popcountll(m));
+                b = read_lane(b, 0);
+                if (keep) pos[u] = b + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+            }
+        }
+        __syncthreads();
+        if (tid == 0 && lctrl[0]) lctrl[1] = atomicAdd(&c[kWcSurv], lctrl[0]);
+        __syncthreads();
+        const uint32_t gbase = lctrl[1];
+#pragma unroll
+        for (int u = 0; u < kRankLoads; ++u) {
+            if (pos[u] != 0xFFFFFFFFu && gbase + pos[u] < (uint32_t)CAP)
+                comp_store<CAP>(surv, (int)(gbase + pos[u]), make_comp(kv[u], tv[u]));
+        }
+    }
+}
+
+template <int W>
+__global__ __launch_bounds__(kRankThreads) void seg_wide_finish_kernel(int32_t k, const int32_t *__restrict__ seg_k,
+                                                                       const uint32_t *__restrict__ ctrl_all,
+                                                                       const uint32_t *__restrict__ surv_all,
+                                                                       uint32_t *__restrict__ out_tie,
+                                                                       double *__restrict__ out_key, int64_t out_stride,
+                                                                       int32_t *__restrict__ out_count) {
+    constexpr int CAP = rank_cap<W>();
+    constexpr int T = kRankThreads;
+    extern __shared__ __attribute__((aligned(16))) uint32_t rank_lds[];
+    uint32_t *arr = rank_lds + kRankCtrlWords;
+    const int tid = threadIdx.x;
+    const int64_t seg = blockIdx.x;
+    int32_t kq = k;
+    if (seg_k) kq = seg_k[seg] < k ? seg_k[seg] : k;
+    const uint32_t *c = ctrl_all + seg * kWideCtrlWords;
+    if (kq <= 0 || c[kWcDone] == 2u) {
+        if (tid == 0) out_count[seg] = 0;
+        return;
+    }
+    const int32_t m = (int32_t)(c[kWcSurv] < (uint32_t)CAP ? c[kWcSurv] : (uint32_t)CAP);
+    int32_t k_eff = (int32_t)c[kWcKeff];
+    if (k_eff > m) k_eff = m;
+    const uint32_t *surv = surv_all + seg * (int64_t)(W * CAP);
+#pragma unroll
+    for (int w = 0; w < W; ++w)
+        for (int32_t i = tid; i < m; i += T) arr[w * CAP + i] = surv[w * CAP + i];
+    __syncthreads();
+    lds_bitonic_sort<W, CAP>(arr, m);
+    emit_sorted<W, CAP>(arr, seg, k_eff, out_tie, out_key, out_stride, out_count);
+}
+
+// ---- dispatch between the two forms
+static std::atomic<int32_t> g_wide_mode{-2};  // -2: not read yet (ANRAG_RANK_WIDE, once)
+static std::atomic<int64_t> g_wide_segments{0}, g_wide_passes{0};
+
+static int32_t wide_mode() {
+    int32_t m = g_wide_mode.load(std::memory_order_relaxed);
+    if (m == -2) {
+        const char *e = getenv("ANRAG_RANK_WIDE");
+        m = e && (e[0] == '0' || e[0] == '1') && e[1] == 0 ? e[0] - '0' : -1;
+        int32_t expect = -2;
+        if (!g_wide_mode.compare_exchange_strong(expect, m)) m = expect;
+    }
+    return m;
+}
+
+// The auto gate: the wide form where the sweep of scripts/measure_rank_one.py (profiles/rank_wide_ab.txt) had it
+// beat the narrow form by more than the narrow form's own spread.  A row: from n_min elements on, up to seg_max
+// segments in a launch.
+struct WideGateRow {
+    int32_t n_min, seg_max;
+};
+// (measured at n = 65,536, 262,144 and 1,000,000, n_seg = 1 ... 256; 1,000,000 past 64 segments was not measured and
+// is not taken; a length between two measured ones takes the shorter one's row; below 65,536: not measured, narrow)
+static const WideGateRow kWideGateF32[] = {{65536, 4}, {262144, 64}};
+static const WideGateRow kWideGateF64[] = {{65536, 8}, {262144, 64}};
+
+bool rank_wide_gate(bool fp64, int32_t n_seg, int32_t n) {
+    const WideGateRow *rows = fp64 ? kWideGateF64 : kWideGateF32;
+    const int n_rows = fp64 ? (int)(sizeof(kWideGateF64) / sizeof(WideGateRow)) : (int)(sizeof(kWideGateF32) / sizeof(WideGateRow));
+    int32_t seg_max = 0;
+    for (int i = 0; i < n_rows; ++i)
+        if (n >= rows[i].n_min) seg_max = rows[i].seg_max;
+    return n_seg <= seg_max;
+}
+
+// does a launch of n_seg segments of n elements take the wide form under the current mode?
+bool rank_wide_wanted(bool fp64, int32_t n_seg, int32_t n) {
+    if (n <= rank_list_cap(fp64) || n_seg <= 0) return false;
+    const int32_t mode = wide_mode();
+    if (mode == 0) return false;
+    return mode == 1 || rank_wide_gate(fp64, n_seg, n);
+}
+int64_t rank_wide_bytes(bool fp64, int32_t n_seg) { return fp64 ? wide_scratch_bytes<3>(n_seg) : wide_scratch_bytes<2>(n_seg); }
+
+static int device_cus(int device) {
+    static std::mutex mu;
+    static int cus[64] = {0};
+    std::lock_guard<std::mutex> lk(mu);
+    if (device < 0 || device >= 64) return 256;
+    if (cus[device] == 0) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || v <= 0) v = 256;
+        cus[device] = v;
+    }
+    return cus[device];
+}
+
+// slice length for a segment of n elements: parts == 0 spreads n_seg * P over the CUs once (n_seg * P in [CUs, CUs +
+// n_seg)); a slice is a multiple of 64 elements and never shorter than kWideMinSlice, so P = ceil(n / slice) may come
+// out smaller than asked for
+static int32_t wide_slice(int device, int32_t n_seg, int32_t n, int32_t parts) {
+    int64_t p = parts > 0 ? parts : (device_cus(device) + n_seg - 1) / n_seg;
+    if (p < 1) p = 1;
+    int64_t slice = ((n + p - 1) / p + 63) / 64 * 64;
+    if (slice < kWideMinSlice) slice = kWideMinSlice;
+    return (int32_t)slice;
+}
+
+template <typename KEY, bool TIE>
+static int launch_seg_wide(int device, hipStream_t st, int32_t n_seg, const KEY *keys, int64_t key_stride,
+                           const uint32_t *ties, int64_t tie_stride, int32_t n, int32_t k, const int32_t *seg_k,
+                           uint32_t *out_tie, double *out_key, int64_t out_stride, int32_t *out_count, char *scratch,
+                           int32_t parts) {
+    constexpr int W = sizeof(KEY) == 4 ? 2 : 3;
+    WideScratch ws;
+    ws.ctrl = reinterpret_cast<uint32_t *>(scratch);
+    ws.hist = ws.ctrl + (int64_t)n_seg * kWideCtrlWords;
+    ws.surv = ws.hist + 2ll * n_seg * kWideBins;
+    const int32_t slice = wide_slice(device, n_seg, n, parts);
+    const dim3 grid((unsigned)((n + slice - 1) / slice), (unsigned)n_seg);
+    int rc = ensure_dynamic_lds(device, reinterpret_cast<const void *>(&seg_wide_finish_kernel<W>), rank_lds_bytes<W>());
+    if (rc) return rc;
+    ANRAG_HIP(hipMemsetAsync(scratch, 0, (size_t)wide_zero_bytes<W>(n_seg), st));
+    for (int pass = 0; pass < wide_passes<W>(); ++pass)
+        seg_wide_pass_kernel<KEY, TIE><<<grid, kRankThreads, 0, st>>>(keys, key_stride, ties, tie_stride, n, slice, k, seg_k,
+                                                                      pass, ws.ctrl, ws.hist);
+    seg_wide_compact_kernel<KEY, TIE><<<grid, kRankThreads, 0, st>>>(keys, key_stride, ties, tie_stride, n, slice, k, seg_k,
+                                                                     ws.ctrl, ws.surv);
+    seg_wide_finish_kernel<W><<<n_seg, kRankThreads, rank_lds_bytes<W>(), st>>>(k, seg_k, ws.ctrl, ws.surv, out_tie, out_key,
+                                                                               out_stride, out_count);
+    ANRAG_HIP(hipGetLastError());
+    g_wide_segments.fetch_add(n_seg, std::memory_order_relaxed);
+    g_wide_passes.fetch_add(wide_passes<W>(), std::memory_order_relaxed);
+    return ANRAG_OK;
+}
+
 template <typename KEY, bool TIE>
 static int launch_seg_sort(int device, hipStream_t st, int32_t n_seg, const KEY *keys, int64_t key_stride,
                            const uint32_t *ties, int64_t tie_stride, int32_t n, int32_t k, const int32_t *seg_k,
-                           uint32_t *out_tie, double *out_key, int64_t out_stride, int32_t *out_count) {
+                           uint32_t *out_tie, double *out_key, int64_t out_stride, int32_t *out_count,
+                           const RankWide &wide = RankWide()) {
     constexpr int W = sizeof(KEY) == 4 ? 2 : 3;
     int rc;
+    // the one place that picks the form: wide needs n > CAP, a scratch block of the caller's pool that holds n_seg
+    // segments, and the mode (or the caller's `form`) to ask for it
+    if (n > rank_cap<W>() && n_seg > 0 && wide.scratch && wide.bytes >= wide_scratch_bytes<W>(n_seg) &&
+        (wide.form == 1 || (wide.form < 0 && rank_wide_wanted(W == 3, n_seg, n))))
+        return launch_seg_wide<KEY, TIE>(device, st, n_seg, keys, key_stride, ties, tie_stride, n, k, seg_k, out_tie, out_key,
+                                         out_stride, out_count, wide.scratch, wide.parts);
     if constexpr (!TIE) {
         static const bool bitonic = getenv("ANRAG_RANK_BITONIC") != nullptr;  // measurements: the network for every segment
         if (n <= radix_cap<W>() && !bitonic) {  // the segment fits the LDS: stable radix sort, no select
@@ -908,12 +1289,12 @@ int rank_list_cap(bool fp64) { return fp64 ? rank_cap<3>() : rank_cap<2>(); }
 
 int launch_rank_sort(int device, hipStream_t st, int32_t n_seg, const void *keys, bool fp64, int64_t key_stride, int32_t n,
                      int32_t k, const int32_t *seg_k, uint32_t *out_rows, double *out_keys, int64_t out_stride,
-                     int32_t *out_count) {
+                     int32_t *out_count, const RankWide &wide) {
     if (fp64)
         return launch_seg_sort<double, false>(device, st, n_seg, static_cast<const double *>(keys), key_stride, nullptr, 0, n, k,
-                                              seg_k, out_rows, out_keys, out_stride, out_count);
+                                              seg_k, out_rows, out_keys, out_stride, out_count, wide);
     return launch_seg_sort<float, false>(device, st, n_seg, static_cast<const float *>(keys), key_stride, nullptr, 0, n, k, seg_k,
-                                         out_rows, out_keys, out_stride, out_count);
+                                         out_rows, out_keys, out_stride, out_count, wide);
 }
 
 int rank_check_maps(int32_t n_legs, const int64_t *const *maps, const int64_t *leg_rows, int64_t id_space) {
@@ -983,7 +1364,7 @@ int launch_rank_tail(const RankTail &t, int32_t c, bool want_ids) {
         }
         ANRAG_HIP(hipGetLastError());
         if ((rc = launch_seg_sort<double, true>(t.device, st, c, t.d_f, id_space, t.d_t, id_space, (int32_t)id_space, t.fuse_n,
-                                                nullptr, t.d_stie, t.d_skey, t.fuse_n, t.d_scnt)))
+                                                nullptr, t.d_stie, t.d_skey, t.fuse_n, t.d_scnt, t.wide)))
             return rc;
         const dim3 grid((unsigned)((out_n + 255) / 256), (unsigned)c);
         rank_emit_fused_kernel<<<grid, 256, 0, st>>>(L, t.d_stie, t.d_skey, t.fuse_n, t.d_scnt, out_n, t.d_out_id,
@@ -1144,7 +1525,17 @@ extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int3
                 const int64_t q1 = std::min<int64_t>(n_queries, q0 + chunk);
                 max_terms_chunk = std::max(max_terms_chunk, legs[l].term_offsets[q1] - legs[l].term_offsets[q0]);
             }
-    const int64_t need = fixed + chunk * per_query + n_legs * (max_terms_chunk * 4 + 256) + (1 << 16);
+    // the wide select's scratch, one block that the launches of a chunk share (they follow each other on the stream): sized
+    // for a full chunk, so a shorter last chunk that asks for it finds it there only if the full ones did
+    const int32_t c_full = (int32_t)std::min<int64_t>(chunk, n_queries);
+    int64_t wide_bytes = 0;
+    for (int l = 0; l < n_legs; ++l) {
+        const bool f64 = legs[l].kind != ANRAG_LEG_DENSE;
+        if (rank_wide_wanted(f64, c_full, (int32_t)leg_rows[l])) wide_bytes = std::max(wide_bytes, rank_wide_bytes(f64, c_full));
+    }
+    if (fuse && !fuse_in_lds && rank_wide_wanted(true, c_full, (int32_t)id_space))
+        wide_bytes = std::max(wide_bytes, rank_wide_bytes(true, c_full));
+    const int64_t need = fixed + chunk * per_query + n_legs * (max_terms_chunk * 4 + 256) + (1 << 16) + wide_bytes;
     int rc;
     if ((rc = ensure_pool(own, own->rank_pool, need))) return rc;
 
@@ -1210,6 +1601,9 @@ extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int3
     int32_t *d_out_cnt = fuse ? d_scnt : cv.take<int32_t>(chunk);
     int64_t *d_expect = expect_id ? cv.take<int64_t>(chunk) : nullptr;
     int32_t *d_rank = expect_id ? cv.take<int32_t>(chunk) : nullptr;
+    RankWide wide;
+    wide.scratch = wide_bytes ? cv.take<char>(wide_bytes) : nullptr;
+    wide.bytes = wide_bytes;
     if (cv.at > own->rank_pool.bytes) {
         set_error("internal: rank scratch carve %lld > pool %lld", (long long)cv.at, (long long)own->rank_pool.bytes);
         return ANRAG_ERR_STATE;
@@ -1237,6 +1631,7 @@ extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int3
     tail.d_out_cnt = d_out_cnt;
     tail.d_expect = d_expect;
     tail.d_rank = d_rank;
+    tail.wide = wide;
     if (fuse_in_lds) {  // the legs' lists, counts, maps, strides and weights: the same for every chunk
         uint64_t tab[6 * ANRAG_WRRF_MAX_LISTS];
         rank_fuse_table(tail, tab);
@@ -1281,7 +1676,8 @@ extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int3
                     rank_count_kernel<float><<<c, kRankThreads, 0, st>>>(tile, ld[l].stride, (int32_t)leg_rows[l], leg_k[l], nullptr,
                                                                         ld[l].doc_of_row, out_n, d_expect, d_rank, d_out_cnt);
                 else if ((rc = launch_seg_sort<float, false>(device, st, c, tile, ld[l].stride, nullptr, 0, (int32_t)leg_rows[l],
-                                                             leg_k[l], nullptr, ld[l].rows, ld[l].row_keys, leg_k[l], ld[l].cnt)))
+                                                             leg_k[l], nullptr, ld[l].rows, ld[l].row_keys, leg_k[l], ld[l].cnt,
+                                                             wide)))
                     return rc;
             } else {
                 const int64_t t0 = g.term_offsets[q0];
@@ -1311,7 +1707,7 @@ extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int3
                                                                          d_out_cnt);
                 else if ((rc = launch_seg_sort<double, false>(device, st, c, tile, ld[l].stride, nullptr, 0,
                                                               (int32_t)leg_rows[l], leg_k[l], ld[l].seg_k, ld[l].rows,
-                                                              ld[l].row_keys, leg_k[l], ld[l].cnt)))
+                                                              ld[l].row_keys, leg_k[l], ld[l].cnt, wide)))
                     return rc;
             }
         }
@@ -1319,5 +1715,87 @@ extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int3
         ANRAG_HIP(hipGetLastError());
         if ((rc = rank_copy_out(tail, c, q0, top_n, out_id, out_score, out_count, out_rank))) return rc;
     }
+    return ANRAG_OK;
+}
+
+extern "C" int anrag_set_rank_wide(int32_t mode) {
+    ANRAG_REQUIRE(mode >= -1 && mode <= 1, "rank wide mode %d (-1 auto, 0 never, 1 wherever a segment exceeds the list cap)", mode);
+    (void)wide_mode();  // the environment is read once, before the first setting
+    g_wide_mode.store(mode, std::memory_order_relaxed);
+    return ANRAG_OK;
+}
+
+extern "C" int anrag_rank_wide_stats(int64_t *segments, int64_t *pass_launches) {
+    if (segments) *segments = g_wide_segments.load(std::memory_order_relaxed);
+    if (pass_launches) *pass_launches = g_wide_passes.load(std::memory_order_relaxed);
+    return ANRAG_OK;
+}
+
+extern "C" int anrag_rank_wide_gate(int32_t fp64, int32_t n_seg, int32_t n, int32_t *out_wide) {
+    ANRAG_REQUIRE(out_wide != nullptr, "out_wide is NULL");
+    *out_wide = n > rank_list_cap(fp64 != 0) && n_seg > 0 && rank_wide_gate(fp64 != 0, n_seg, n) ? 1 : 0;
+    return ANRAG_OK;
+}
+
+extern "C" int anrag_debug_rank_select(anrag_index *idx, const void *keys, int32_t fp64, const uint32_t *ties, int32_t n_seg,
+                                       int64_t key_stride, int32_t n, int32_t k, const int32_t *seg_k, int32_t form,
+                                       int32_t parts, uint32_t *out_rows, double *out_keys, int32_t *out_count) {
+    ANRAG_REQUIRE(idx != nullptr, "index handle is NULL");
+    ANRAG_REQUIRE(keys != nullptr && out_rows != nullptr && out_count != nullptr, "keys, out_rows or out_count is NULL");
+    ANRAG_REQUIRE(n_seg >= 1 && n_seg <= 65535, "n_seg %d out of range [1, 65535]", n_seg);
+    ANRAG_REQUIRE(n >= 1 && n < 0x7FFFFFFF && key_stride >= n, "n %d / key_stride %lld out of range", n, (long long)key_stride);
+    ANRAG_REQUIRE(k >= 1, "k must be positive");
+    ANRAG_REQUIRE(form >= -1 && form <= 1 && parts >= 0, "form %d / parts %d out of range", form, parts);
+    ANRAG_REQUIRE(!ties || fp64, "tie words come with fp64 keys (the fused sums)");
+    const int32_t cap = rank_list_cap(fp64 != 0);
+    const int32_t kk = k < cap ? k : cap;  // the select's envelope, as anrag_rank_batch requires of its lists
+    std::lock_guard<std::mutex> lock(idx->mu);
+    DeviceGuard guard(idx->device);
+    if (!guard.ok) {
+        set_error("hipSetDevice(%d) failed", idx->device);
+        return ANRAG_ERR_HIP;
+    }
+    if (int rc = settle_pipeline(idx)) return rc;
+    hipStream_t st = idx->primary;
+    const int64_t esz = fp64 ? 8 : 4;
+    const bool wide_ok = form != 0;
+    void *d_keys = nullptr;
+    uint32_t *d_ties = nullptr, *d_rows = nullptr;
+    int32_t *d_segk = nullptr, *d_cnt = nullptr;
+    double *d_okeys = nullptr;
+    RankWide wide;
+    wide.form = form;
+    wide.parts = parts;
+    auto layout = [&](Carver &cv) {
+        d_keys = cv.take<char>((int64_t)n_seg * key_stride * esz);
+        d_ties = ties ? cv.take<uint32_t>((int64_t)n_seg * key_stride) : nullptr;
+        d_segk = seg_k ? cv.take<int32_t>(n_seg) : nullptr;
+        d_rows = cv.take<uint32_t>((int64_t)n_seg * kk);
+        d_okeys = out_keys ? cv.take<double>((int64_t)n_seg * kk) : nullptr;
+        d_cnt = cv.take<int32_t>(n_seg);
+        wide.bytes = wide_ok ? rank_wide_bytes(fp64 != 0, n_seg) : 0;
+        wide.scratch = wide_ok ? cv.take<char>(wide.bytes) : nullptr;
+    };
+    if (int rc = carve_pool(idx, idx->rank_pool, 256, layout)) return rc;
+    ANRAG_HIP(hipMemcpyAsync(d_keys, keys, (size_t)((int64_t)n_seg * key_stride * esz), hipMemcpyHostToDevice, st));
+    if (ties) ANRAG_HIP(hipMemcpyAsync(d_ties, ties, (size_t)n_seg * key_stride * 4, hipMemcpyHostToDevice, st));
+    if (seg_k) ANRAG_HIP(hipMemcpyAsync(d_segk, seg_k, (size_t)n_seg * 4, hipMemcpyHostToDevice, st));
+    ANRAG_HIP(hipMemsetAsync(d_rows, 0, (size_t)n_seg * kk * 4, st));  // what the kernels leave alone comes back as zero
+    if (out_keys) ANRAG_HIP(hipMemsetAsync(d_okeys, 0, (size_t)n_seg * kk * 8, st));
+    int rc;
+    {
+        LaunchTimer t(idx, ANRAG_KERNEL_SELECT, st, n_seg);  // (anrag_profile_enable: the select's launches, first to last)
+        if (ties)
+            rc = launch_seg_sort<double, true>(idx->device, st, n_seg, static_cast<const double *>(d_keys), key_stride, d_ties,
+                                               key_stride, n, kk, d_segk, d_rows, d_okeys, kk, d_cnt, wide);
+        else
+            rc = launch_rank_sort(idx->device, st, n_seg, d_keys, fp64 != 0, key_stride, n, kk, d_segk, d_rows, d_okeys, kk,
+                                  d_cnt, wide);
+    }
+    if (rc) return rc;
+    ANRAG_HIP(hipMemcpyAsync(out_rows, d_rows, (size_t)n_seg * kk * 4, hipMemcpyDeviceToHost, st));
+    if (out_keys) ANRAG_HIP(hipMemcpyAsync(out_keys, d_okeys, (size_t)n_seg * kk * 8, hipMemcpyDeviceToHost, st));
+    ANRAG_HIP(hipMemcpyAsync(out_count, d_cnt, (size_t)n_seg * 4, hipMemcpyDeviceToHost, st));
+    ANRAG_HIP(hipStreamSynchronize(st));
     return ANRAG_OK;
 }

@@ -102,6 +102,7 @@ struct ShardDev {  // one shard's share of one leg
     int32_t *stage_cnt = nullptr;
     std::vector<int32_t> h_segk;
     std::vector<int64_t> h_off;
+    RankWide wide;  // the wide select's scratch, where the mode takes it for this shard's block
 };
 
 struct LegDev {
@@ -308,6 +309,8 @@ extern "C" int anrag_shard_group_rank_batch(const anrag_group_rank_leg *legs, in
     int32_t *d_scnt = nullptr, *d_out_cnt = nullptr, *d_rank = nullptr;
     uint64_t *d_fuse_legs = nullptr;
     int64_t *d_out_id = nullptr, *d_expect = nullptr;
+    RankWide fuse_wide;
+    const int32_t c_full = (int32_t)std::min<int64_t>(chunk, n_queries);  // segments of a full chunk's sort launches
     std::vector<PoolUse> pools;
     for (anrag_index *o : owners) pools.push_back(PoolUse{o, Carver(nullptr)});
     auto pool_of = [&](anrag_index *ix) -> Carver & {
@@ -335,6 +338,8 @@ extern "C" int anrag_shard_group_rank_batch(const anrag_group_rank_leg *legs, in
                 sd.list_rows = cv.take<uint32_t>(chunk * sd.k);
                 sd.list_keys = cv.take<double>(chunk * sd.k);
                 sd.list_cnt = cv.take<int32_t>(chunk);
+                sd.wide.bytes = rank_wide_wanted(!dense, c_full, (int32_t)sd.rows) ? rank_wide_bytes(!dense, c_full) : 0;
+                sd.wide.scratch = sd.wide.bytes ? cv.take<char>(sd.wide.bytes) : nullptr;
                 if (!sd.in_place) {
                     sd.stage_rows = hv.take<uint32_t>(chunk * sd.k);
                     sd.stage_keys = hv.take<double>(chunk * sd.k);
@@ -366,6 +371,8 @@ extern "C" int anrag_shard_group_rank_batch(const anrag_group_rank_leg *legs, in
         d_out_cnt = fuse ? d_scnt : hv.take<int32_t>(chunk);
         d_expect = expect_id ? hv.take<int64_t>(chunk) : nullptr;
         d_rank = expect_id ? hv.take<int32_t>(chunk) : nullptr;
+        fuse_wide.bytes = fuse && !fuse_in_lds && rank_wide_wanted(true, c_full, (int32_t)id_space) ? rank_wide_bytes(true, c_full) : 0;
+        fuse_wide.scratch = fuse_wide.bytes ? hv.take<char>(fuse_wide.bytes) : nullptr;
     };
     carve();
     int rc;
@@ -438,6 +445,7 @@ extern "C" int anrag_shard_group_rank_batch(const anrag_group_rank_leg *legs, in
     tail.d_out_cnt = d_out_cnt;
     tail.d_expect = d_expect;
     tail.d_rank = d_rank;
+    tail.wide = fuse_wide;
     if (fuse_in_lds) {
         uint64_t tab[6 * ANRAG_WRRF_MAX_LISTS];
         rank_fuse_table(tail, tab);
@@ -476,7 +484,7 @@ extern "C" int anrag_shard_group_rank_batch(const anrag_group_rank_leg *legs, in
                     return r;
             }
             return launch_rank_sort(sd.device, st, c, tile, false, sd.stride, (int32_t)sd.rows, sd.k, nullptr, sd.list_rows,
-                                    sd.list_keys, sd.k, sd.list_cnt);
+                                    sd.list_keys, sd.k, sd.list_cnt, sd.wide);
         }
         const int64_t t0 = g.term_offsets[q0];
         const int64_t nt = g.term_offsets[q0 + c] - t0;
@@ -496,7 +504,7 @@ extern "C" int anrag_shard_group_rank_batch(const anrag_group_rank_leg *legs, in
                                               tile + (int64_t)g0 * sd.stride, sd.stride)))
                 return r;
         return launch_rank_sort(sd.device, st, c, tile, true, sd.stride, (int32_t)sd.rows, sd.k, sd.seg_k, sd.list_rows,
-                                sd.list_keys, sd.k, sd.list_cnt);
+                                sd.list_keys, sd.k, sd.list_cnt, sd.wide);
     };
     auto run = [&]() -> int {
         for (int64_t q0 = 0; q0 < n_queries; q0 += chunk) {

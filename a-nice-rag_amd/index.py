@@ -31,6 +31,53 @@ def rank_caps() -> Tuple[int, int]:
     return a.value, b.value
 
 
+def set_rank_wide(mode: int) -> None:
+    """`anrag_set_rank_wide`: which form of the select a ranking takes for segments longer than the list cap --
+    -1 auto (the measured gate), 0 never wide, 1 always wide.  Process-wide."""
+    nat.check(nat.load_library().anrag_set_rank_wide(int(mode)))
+
+
+def rank_wide_stats() -> Tuple[int, int]:
+    """(segments sorted by the wide form, pass launches enqueued for them), cumulative and process-wide."""
+    a, b = C.c_int64(), C.c_int64()
+    nat.check(nat.load_library().anrag_rank_wide_stats(C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def rank_wide_gate(fp64: bool, n_seg: int, n: int) -> bool:
+    """Does a launch of `n_seg` segments of `n` scores take the wide form in auto mode?"""
+    w = C.c_int32()
+    nat.check(nat.load_library().anrag_rank_wide_gate(int(bool(fp64)), int(n_seg), int(n), C.byref(w)))
+    return bool(w.value)
+
+
+def debug_rank_select(index, keys: np.ndarray, n: int, k: int, ties: Optional[np.ndarray] = None, seg_k=None,
+                      form: int = -1, parts: int = 0):
+    """`anrag_debug_rank_select`: the select + sort of a ranking over planted scores.  keys [n_seg, stride] float32 or
+    float64 (the first n of a row count), ties (optional, float64 keys) [n_seg, stride] uint32.
+    -> (rows [n_seg, kk] uint32, scores [n_seg, kk] float64, counts [n_seg] int32), kk = min(k, the list cap); entries
+    past a segment's count are zero."""
+    keys = np.ascontiguousarray(keys)
+    assert keys.ndim == 2 and keys.dtype in (np.float32, np.float64)
+    fp64 = keys.dtype == np.float64
+    n_seg, stride = keys.shape
+    kk = min(int(k), rank_caps()[1 if fp64 else 0])
+    if ties is not None:
+        ties = np.ascontiguousarray(ties, dtype=np.uint32)
+        assert ties.shape == keys.shape
+    if seg_k is not None:
+        seg_k = np.ascontiguousarray(seg_k, dtype=np.int32)
+        assert seg_k.shape == (n_seg,)
+    rows = np.zeros((n_seg, kk), np.uint32)
+    scores = np.zeros((n_seg, kk), np.float64)
+    counts = np.zeros(n_seg, np.int32)
+    nat.check(nat.load_library().anrag_debug_rank_select(
+        index.handle, keys.ctypes.data, int(fp64), ties.ctypes.data if ties is not None else None, n_seg, stride, int(n),
+        int(k), seg_k.ctypes.data if seg_k is not None else None, int(form), int(parts), rows.ctypes.data,
+        scores.ctypes.data, counts.ctypes.data))
+    return rows, scores, counts
+
+
 def _fill_leg(slot, leg: dict, i: int, n_queries: int, keep: list) -> None:
     """The operands of one leg into its C struct (`RankLeg` / `GroupRankLeg`: the shared fields); `keep` holds the arrays."""
     ix = leg["index"]

@@ -192,7 +192,7 @@ class RetrievalEvaluationSystem:
         except Exception as e:
             from ._native import AnragError
 
-            if isinstance(e, AnragError) and e.code in (-100, -5, -6):
+            if isinstance(e, AnragError) and (e.code in (-100, -5, -6) or getattr(e, "surface", False)):
                 raise
             logger.error(f"Error in retrieval processing: {e}")
             return []
@@ -226,6 +226,11 @@ class RetrievalEvaluationSystem:
     def _rank_route(self, source_enum, active, query_embeddings, query_tokens, query_text, want_bm25, bm25,
                     bm25_sections, bm25_section_ids, similarity_k, common_sections_n, model_weights,
                     filename_type_filter, wrrf_k) -> Optional[List[str]]:
+        if self.RANK_ONE_CALL:
+            ids = self._rank_one_call(source_enum, active, query_embeddings, query_tokens, query_text, want_bm25, bm25,
+                                      similarity_k, common_sections_n, model_weights, filename_type_filter, wrrf_k)
+            if ids is not None:
+                return ids
         se = self.search_engine
         lists, weights = [], []
         for key, df in active:
@@ -249,6 +254,37 @@ class RetrievalEvaluationSystem:
             gids = lists[0][:common_sections_n]
         names = self._gid_tables[source_enum]["names"]
         return [names[g] for g in gids.tolist()]
+
+    RANK_ONE_CALL = True  # a single ids-only query as ONE `anrag_rank_batch` (False: the per-leg calls; for A/B runs)
+
+    def _rank_one_call(self, source_enum, active, query_embeddings, query_tokens, query_text, want_bm25, bm25,
+                       similarity_k, common_sections_n, model_weights, filename_type_filter, wrrf_k) -> Optional[List[str]]:
+        """One query through `_rank_batch` as a list of one: scores, selects and fusion in one library call with one
+        host sync, where the per-leg route makes a call, a sort and a sync per leg and one more for the fusion.  Taken
+        when every leg lives on one plain index (no shard group), the embeddings are float32 (a float64 query is scored
+        in fp64 by the per-leg route) and the lists fit `anrag_rank_caps`; None = not taken.  Among rows that score
+        exactly +-0.0 this route ties by row, as every list call does (DESIGN, "Order of equal scores")."""
+        from ._native import AnragError
+
+        if self._on_shard_group(self.embeddings_data.get(source_enum, {}), bm25):
+            return None
+        if want_bm25 and not (query_tokens or query_text):
+            logger.warning("BM25 search requested but no query_text or query_tokens provided - skipping BM25")
+        params = dict(similarity_k=similarity_k, common_sections_n=common_sections_n, info_source=source_enum.value,
+                      model_weights=model_weights, filename_type_filter=filename_type_filter, use_hybrid_search=want_bm25,
+                      wrrf_k=wrrf_k, use_reranker=False)
+        query = dict(query_embeddings=query_embeddings, query_tokens=query_tokens, query_text=query_text)
+        try:
+            rows = self._rank_batch([query], params)
+        except AnragError as e:
+            if e.code == -1:  # ANRAG_ERR_INVALID: outside the batched ranking's envelope (k above the caps, ...)
+                logger.warning(f"Single-call ranking not applicable, taking the per-leg route: {e}")
+                return None
+            e.surface = True  # a failed launch, copy or allocation is not a reason to answer differently
+            raise
+        if rows is None:
+            return None
+        return self._names_of(source_enum, rows)[0]
 
     # ------------------------------------------------------------------ query lists
     @staticmethod

@@ -426,6 +426,34 @@ int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int32_t n_queri
                      int32_t *out_count, const int64_t *expect_id, int32_t *out_rank);
 /* Largest list a dense (fp32 scores) / BM25 or fused (fp64 scores) ranking of anrag_rank_batch can return. */
 int anrag_rank_caps(int32_t *out_k_max_fp32, int32_t *out_k_max_fp64);
+/* The select behind a ranking has two forms for a segment (one query's scores of one leg, or its fused sums) longer
+ * than the list cap: narrow = one workgroup per segment, right for lists of queries; wide = a segment cut into slices
+ * across the whole device (a pass launch per 11-bit digit, a compaction launch, a finish launch; no host sync in
+ * between), for one or a few queries over a large corpus.  Same order, same output bits.
+ * mode: -1 auto (the measured gate table, anrag_rank_wide_gate; the default), 0 never, 1 wherever a segment exceeds the
+ * cap.  Process-wide (anrag_rank_batch spans indexes); the environment's ANRAG_RANK_WIDE=0|1 is read once, before the
+ * first call.  anrag_shard_group_rank_batch's per-shard sorts follow the same setting. */
+int anrag_set_rank_wide(int32_t mode);
+/* Cumulative, process-wide: segments sorted by the wide form and pass launches enqueued for them (a wide launch
+ * enqueues the worst case, 6 passes for fp32 scores and 9 for fp64, whatever its segments turn out to need). */
+int anrag_rank_wide_stats(int64_t *segments, int64_t *pass_launches);
+/* The auto gate alone: *out_wide = 1 when a launch of n_seg segments of n scores (fp64 != 0: fp64 scores) takes the
+ * wide form in auto mode. */
+int anrag_rank_wide_gate(int32_t fp64, int32_t n_seg, int32_t n, int32_t *out_wide);
+/* For tests (tests/test_gpu_rank_wide.py): planted score arrays through exactly the production launch path of the
+ * select, on the index's primary stream and out of its rank pool; waits and copies out.  All arrays are HOST arrays.
+ * keys [n_seg][key_stride] fp32 (fp64 != 0: fp64), n <= key_stride scores per segment, -inf = not a candidate; ties
+ * (nullable, fp64 keys only) [n_seg][key_stride] = the tie-break words, unique inside a segment (the fused form), else
+ * ties go to the lower position; seg_k (nullable) [n_seg] per-segment k, 0 = skip.  k above the list cap
+ * (anrag_rank_caps) is cut to it, as anrag_rank_batch requires of its lists: kk = min(k, cap).
+ * form: 0 narrow, 1 wide (where n exceeds the cap), -1 what the current mode picks.  parts: 0 lets the launcher choose
+ * the number of slices P of the wide form, else P = parts; either way a slice is a multiple of 64 scores and at least
+ * 4096, slice = max(4096, roundup64(ceil(n / P))), and ceil(n / slice) workgroups share a segment.
+ * out_rows [n_seg][kk], out_keys (nullable) [n_seg][kk] the scores as fp64, out_count [n_seg] = min(kk, candidates);
+ * entries past a segment's count come back as zero (the kernels do not write them). */
+int anrag_debug_rank_select(anrag_index *idx, const void *keys, int32_t fp64, const uint32_t *ties, int32_t n_seg,
+                            int64_t key_stride, int32_t n, int32_t k, const int32_t *seg_k, int32_t form, int32_t parts,
+                            uint32_t *out_rows, double *out_keys, int32_t *out_count);
 
 /* ------------------------------------------------------------------ sharded merge
  * After an all-gather of every shard's k candidates: merge n_lists sorted lists of
