@@ -81,6 +81,8 @@ _SIGNATURES = {
     "anrag_set_batched_precision": [_p, _i32],
     "anrag_set_dense_prefilter": [_p, _i32],
     "anrag_dense_prefilter_stats": [_p, C.POINTER(_i64), C.POINTER(_i64)],
+    "anrag_set_scan_pairing": [_p, _i32],
+    "anrag_scan_pair_stats": [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32)],
     "anrag_dense_scores": [_p, _p, _p],
     "anrag_bm25_load": [_p, _p, _i64, _p, _p, _p, _p, _i64, _f64, _f64, _f64, _p, _p, _i64],
     "anrag_bm25_search": [_p, _p, _i32, _i32, _p, _i32, _p, _p, _p],

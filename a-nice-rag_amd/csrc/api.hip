@@ -202,6 +202,7 @@ static int flush_lanes(anrag_index *idx) {
 }
 
 int sync_all(anrag_index *idx) {
+    const int held_rc = pair_flush(idx);  // a query held back for a partner is launched before anything is waited for
     if (idx->lanes.active) {
         int rc = flush_lanes(idx);
         for (int l = 0; l < kScanLanesMax; ++l) ANRAG_HIP(hipStreamSynchronize(idx->lane[l].st));
@@ -212,11 +213,13 @@ int sync_all(anrag_index *idx) {
     ANRAG_HIP(hipStreamSynchronize(idx->secondary));
     ANRAG_HIP(hipStreamSynchronize(idx->fusion));
     idx->hyb_outstanding = false;
-    return ANRAG_OK;
+    idx->last_scan_slot = -1;
+    return held_rc;
 }
 
 // Entry points outside the hybrid pipeline reuse its buffers: let an outstanding pipeline drain first.
 int settle_pipeline(anrag_index *idx) {
+    if (int rc = pair_flush(idx)) return rc;
     if (!idx->hyb_outstanding) return ANRAG_OK;
     return sync_all(idx);
 }
@@ -336,7 +339,7 @@ static int launch_dense_leg_f64(anrag_index *idx, hipStream_t st, const double *
     return launch_dense_prefilter_rescore_f64(idx, st, idx->d_query_f64, w, k);
 }
 
-#define ANRAG_ENTER(idx)                                                   \
+#define ANRAG_ENTER_HOLDING(idx)                                           \
     ANRAG_REQUIRE((idx) != nullptr, "index handle is NULL");              \
     std::lock_guard<std::mutex> lock__((idx)->mu);                        \
     ::anrag::DeviceGuard guard__((idx)->device);                          \
@@ -344,6 +347,13 @@ static int launch_dense_leg_f64(anrag_index *idx, hipStream_t st, const double *
         ::anrag::set_error("hipSetDevice(%d) failed", (idx)->device);     \
         return ANRAG_ERR_HIP;                                             \
     }
+
+// Every entry point but the two that know about a held query (anrag_hybrid_search_device, which pairs it, and
+// anrag_scan_pair_stats, which reports it) launches it first: a query held back for a partner (pair_flush) is on the
+// device no later than the first call that could observe its answer or change what it runs on.
+#define ANRAG_ENTER(idx)                                                   \
+    ANRAG_ENTER_HOLDING(idx)                                               \
+    if (int held_rc__ = ::anrag::pair_flush(idx)) return held_rc__;
 
 }  // namespace anrag
 
@@ -403,6 +413,7 @@ int anrag_index_create(int device, anrag_index **out) {
     if (const char *env = getenv("ANRAG_SCAN_LANES")) { const int v = atoi(env); idx->n_lanes = v <= 0 ? 0 : (v >= 4 ? 4 : (v == 3 ? 2 : v)); }
     if (const char *env = getenv("ANRAG_DENSE_PREFILTER")) { const int v = atoi(env); idx->pf_mode = v < 0 ? -1 : (v > 2 ? 2 : v); }
     if (const char *env = getenv("ANRAG_DENSE_F64_PREFILTER")) idx->f64_pf_on = atoi(env) != 0;
+    if (const char *env = getenv("ANRAG_SCAN_PAIR")) { const int v = atoi(env); idx->scan_pair_mode = v <= 0 ? 0 : (v >= 2 ? 2 : 1); }
     for (int b = 0; b < kPipeSlots && e == hipSuccess; ++b) {
         e = hipEventCreateWithFlags(&idx->ev_scan[b], hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&idx->ev_bm25[b], hipEventDisableTiming);
@@ -1067,6 +1078,7 @@ static int hybrid_enqueue_group(anrag_index *idx, TailMode tail, const GroupQuer
         if ((rc = launch_dense_scan_group(idx, P, qs, n, k, d_allow_dense, nullptr, slot, 0, nullptr, /*finish_later*/ true)))
             return rc;
         ANRAG_HIP(hipEventRecord(idx->ev_scan[slot[0]], P));
+        idx->last_scan_slot = slot[0];
     }
     hipStream_t T = tail == kTailFuse ? S : F;
     {  // the BM25 legs of the group: one launch, a workgroup set per query
@@ -1209,20 +1221,107 @@ int anrag_hybrid_candidates_group_device(anrag_index *idx, const float *const *d
     return ANRAG_OK;
 }
 
+}  // extern "C"
+
+namespace anrag {
+// Launch the fused hybrid query that anrag_hybrid_search_device holds back for a partner, alone.  The caller holds the
+// index's lock and has set its device.  An error of the launch is the caller's to return.
+int pair_flush(anrag_index *idx) {
+    anrag_index::PendingQuery &p = idx->pair_pending;
+    if (!p.held) return ANRAG_OK;
+    p.held = false;
+    return hybrid_enqueue(idx, kTailFuse, p.d_query, p.d_terms, p.n_terms, p.k, p.w_dense, p.w_bm25, p.wrrf_k, p.top_n,
+                          p.allow_dense, p.allow_bm25, p.d_out, p.d_count);
+}
+}  // namespace anrag
+
+extern "C" {
+
+// Does a pair pass of the int8 shadow scan serve this fused query on the pipeline route?  (The int8 prefilter answers
+// it, the shape has a pair kernel for the filtered / unfiltered form, and the index runs on its own three streams: a
+// caller who passed streams in observes `secondary` directly, so nothing of theirs is ever held back.)
+static bool pair_applies(const anrag_index *idx, const float *d_query, int32_t k, double w_dense,
+                         const uint32_t *d_allow_dense) {
+    return idx->scan_pair_mode != 0 && d_query != nullptr && idx->d_emb != nullptr && w_dense > 0.0 && idx->pf_on &&
+           idx->pf_form == kPrefilterInt8 && k <= kListLen && idx->primary == idx->own_primary &&
+           idx->secondary == idx->own_secondary && idx->fusion == idx->own_fusion &&
+           dense_prefilter_pairs(idx, d_allow_dense != nullptr && idx->d_dense_src != nullptr);
+}
+
+// Pairing of single calls ("K1F8 pair pass").  Where pair_applies, two consecutive calls with identical
+// parameters become ONE group of 2 -- one walk of the int8 image, one launch per stage:
+//   1. a query is held and this one has its parameters: enqueue {held, this} as a group of 2;
+//   2. a query is held and the parameters differ: the held one is launched alone, then 3;
+//   3. the pipeline's latest scan has not finished (nothing launched now would start before it ends): hold this query;
+//   4. otherwise launch it alone, as ever -- one query on an idle device is never held.
+// Mode 2 (tests) holds in step 3 whatever the device does.  A held query is launched by the next call of any other
+// entry point on the index (ANRAG_ENTER), by sync_all and by settle_pipeline.
 int anrag_hybrid_search_device(anrag_index *idx, const float *d_query, const int32_t *d_term_ids, int32_t n_terms,
                                int32_t similarity_k, double w_dense, double w_bm25, double wrrf_k, int32_t top_n,
                                const uint32_t *d_allow_dense_bits, const uint32_t *d_allow_bm25_bits,
                                anrag_candidate *d_out, int32_t *d_count) {
-    ANRAG_ENTER(idx);
-    ANRAG_REQUIRE(d_out && d_count, "NULL operand");
-    ANRAG_REQUIRE(similarity_k > 0 && similarity_k <= ANRAG_FUSED_K_MAX, "fused hybrid serves 1 <= similarity_k <= %d",
-                  ANRAG_FUSED_K_MAX);
-    ANRAG_REQUIRE(top_n > 0 && top_n <= 2 * ANRAG_FUSED_K_MAX, "top_n %d out of range", top_n);
-    if (hybrid_lane_route(idx) && d_query != nullptr && (!d_allow_dense_bits || idx->d_dense_src))
-        return hybrid_lane_enqueue(idx, kTailFuse, GroupQuery{d_query, d_term_ids, n_terms, d_out, d_count}, similarity_k,
-                                   w_dense, w_bm25, wrrf_k, top_n, d_allow_dense_bits, d_allow_bm25_bits);
+    ANRAG_ENTER_HOLDING(idx);
+    anrag_index::PendingQuery &p = idx->pair_pending;
+    const bool valid = d_out && d_count && similarity_k > 0 && similarity_k <= ANRAG_FUSED_K_MAX && top_n > 0 &&
+                       top_n <= 2 * ANRAG_FUSED_K_MAX;
+    const bool lane = valid && hybrid_lane_route(idx) && d_query != nullptr && (!d_allow_dense_bits || idx->d_dense_src);
+    if (!valid || lane || !pair_applies(idx, d_query, similarity_k, w_dense, d_allow_dense_bits)) {
+        if (int rc = pair_flush(idx)) return rc;
+        ANRAG_REQUIRE(d_out && d_count, "NULL operand");
+        ANRAG_REQUIRE(similarity_k > 0 && similarity_k <= ANRAG_FUSED_K_MAX, "fused hybrid serves 1 <= similarity_k <= %d",
+                      ANRAG_FUSED_K_MAX);
+        ANRAG_REQUIRE(top_n > 0 && top_n <= 2 * ANRAG_FUSED_K_MAX, "top_n %d out of range", top_n);
+        if (lane)
+            return hybrid_lane_enqueue(idx, kTailFuse, GroupQuery{d_query, d_term_ids, n_terms, d_out, d_count}, similarity_k,
+                                       w_dense, w_bm25, wrrf_k, top_n, d_allow_dense_bits, d_allow_bm25_bits);
+        return hybrid_enqueue(idx, kTailFuse, d_query, d_term_ids, n_terms, similarity_k, w_dense, w_bm25, wrrf_k, top_n,
+                              d_allow_dense_bits, d_allow_bm25_bits, d_out, d_count);
+    }
+    if (p.held) {
+        if (p.k == similarity_k && p.top_n == top_n && p.w_dense == w_dense && p.w_bm25 == w_bm25 && p.wrrf_k == wrrf_k &&
+            p.allow_dense == d_allow_dense_bits && p.allow_bm25 == d_allow_bm25_bits) {
+            p.held = false;
+            const GroupQuery g[2] = {GroupQuery{p.d_query, p.d_terms, p.n_terms, p.d_out, p.d_count},
+                                     GroupQuery{d_query, d_term_ids, n_terms, d_out, d_count}};
+            return hybrid_enqueue_group(idx, kTailFuse, g, 2, similarity_k, w_dense, w_bm25, wrrf_k, top_n, d_allow_dense_bits,
+                                        d_allow_bm25_bits);
+        }
+        if (int rc = pair_flush(idx)) return rc;
+    }
+    const bool busy = idx->last_scan_slot >= 0 && hipEventQuery(idx->ev_scan[idx->last_scan_slot]) == hipErrorNotReady;
+    if (idx->scan_pair_mode == 2 || busy) {
+        p.held = true;
+        p.d_query = d_query;
+        p.d_terms = d_term_ids;
+        p.n_terms = n_terms;
+        p.d_out = d_out;
+        p.d_count = d_count;
+        p.k = similarity_k;
+        p.top_n = top_n;
+        p.w_dense = w_dense;
+        p.w_bm25 = w_bm25;
+        p.wrrf_k = wrrf_k;
+        p.allow_dense = d_allow_dense_bits;
+        p.allow_bm25 = d_allow_bm25_bits;
+        return ANRAG_OK;
+    }
     return hybrid_enqueue(idx, kTailFuse, d_query, d_term_ids, n_terms, similarity_k, w_dense, w_bm25, wrrf_k, top_n,
                           d_allow_dense_bits, d_allow_bm25_bits, d_out, d_count);
+}
+
+int anrag_set_scan_pairing(anrag_index *idx, int32_t mode) {
+    ANRAG_ENTER(idx);
+    ANRAG_REQUIRE(mode >= 0 && mode <= 2, "scan pairing mode %d: 0 off, 1 auto, 2 always hold the odd query", mode);
+    idx->scan_pair_mode = mode;
+    return ANRAG_OK;
+}
+
+int anrag_scan_pair_stats(anrag_index *idx, int64_t *pair_passes, int64_t *single_passes, int32_t *pending) {
+    ANRAG_ENTER_HOLDING(idx);  // reads without launching the held query
+    if (pair_passes) *pair_passes = idx->pf_pair_passes;
+    if (single_passes) *single_passes = idx->pf_single_passes;
+    if (pending) *pending = idx->pair_pending.held ? 1 : 0;
+    return ANRAG_OK;
 }
 
 // ---- host-pointer hybrid query.  Staging is per pipeline slot (pinned host block + device operands + result
@@ -1296,6 +1395,7 @@ struct HybridHostQuery {
     bool dense = false;
 
     int prepare(std::unique_lock<std::mutex> &lock) {
+        if (int rc = pair_flush(idx)) return rc;  // a held device-pointer query goes first (the lock is held)
         ANRAG_REQUIRE(out_id && out_score && out_count, "NULL operand");
         ANRAG_REQUIRE(similarity_k > 0 && similarity_k <= ANRAG_FUSED_K_MAX, "fused hybrid serves 1 <= similarity_k <= %d",
                       ANRAG_FUSED_K_MAX);

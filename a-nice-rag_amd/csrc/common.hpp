@@ -275,6 +275,21 @@ struct anrag_index {
     float *d_pf_thr = nullptr;          // [kPipeSlots]
     unsigned long long *d_pf_survivors = nullptr;  // cumulative survivors
     int64_t pf_queries = 0;             // cumulative queries through the prefilter
+    // the int8 scan's pair pass (two queries per walk of the image) and the pairing of single fused hybrid calls (api.hip)
+    int32_t scan_pair_mode = 1;         // ANRAG_SCAN_PAIR / anrag_set_scan_pairing: 0 off, 1 auto, 2 always hold the odd query
+    int64_t pf_pair_passes = 0, pf_single_passes = 0;  // int8 scan passes by form (anrag_scan_pair_stats)
+    struct PendingQuery {               // one fused hybrid query held back for a partner
+        bool held = false;
+        const float *d_query = nullptr;
+        const int32_t *d_terms = nullptr;
+        int32_t n_terms = 0;
+        anrag_candidate *d_out = nullptr;
+        int32_t *d_count = nullptr;
+        int32_t k = 0, top_n = 0;
+        double w_dense = 0, w_bm25 = 0, wrrf_k = 0;
+        const uint32_t *allow_dense = nullptr, *allow_bm25 = nullptr;
+    } pair_pending;
+    int last_scan_slot = -1;            // slot whose ev_scan the pipeline's latest scan launch recorded
 
     int64_t hbm_bytes = 0;
     int64_t bm25_hbm_bytes = 0;
@@ -314,6 +329,7 @@ struct LaunchTimer {
 };
 
 int drain_profile(anrag_index *idx);
+int pair_flush(anrag_index *idx);       // launch the fused hybrid query held back for a partner, if any (api.hip)
 int sync_all(anrag_index *idx);         // wait for the index's three streams
 int settle_pipeline(anrag_index *idx);  // ... only when pipeline queries may be outstanding
 int ensure_pool(anrag_index *idx, DevicePool &pool, int64_t bytes);  // grow-only (contents are NOT kept)
@@ -348,6 +364,7 @@ bool dense_scan_has_shape(const anrag_index *idx);  // a shaped (not the generic
 // K1F / K1F8, the prefiltered dense top-k (dense_prefilter.hip): fp16 or int8 shadow scan -> threshold -> exact
 // rescoring of survivors
 bool dense_prefilter_has_shape(const anrag_index *idx);
+bool dense_prefilter_pairs(const anrag_index *idx, bool filtered);  // the int8 form has a pair kernel for this shape
 int dense_prefilter_vgprs(const anrag_index *idx);  // the largest K1F kernel that runs beside K3 (0: no shape)
 constexpr int32_t kPrefilterFp16 = 1, kPrefilterInt8 = 2;  // the forms (K1F, K1F8): anrag_set_dense_prefilter's modes
 int64_t dense_prefilter_bytes(int64_t n_rows, int32_t dim, int32_t form);

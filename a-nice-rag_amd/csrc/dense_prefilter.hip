@@ -379,18 +379,31 @@ __global__ __launch_bounds__(kScanThreads) void dense_prefilter_i8_convert_kerne
 // and the top-k offer are then computed once per batch for all its rows.
 // amdgpu_waves_per_eu(4): <= 128 VGPRs, so that K3's waves fit beside a scan wave on every SIMD (bm25.hip); the
 // unconstrained schedule of the 768-d shape took 133-136.
-template <int G, int CH, int R, bool FILTER>
-__global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(4))) void dense_prefilter_i8_scan_kernel(
-    const i32x4 *__restrict__ img, const f32x4 *__restrict__ meta, PrefilterQueries Q, int64_t n_rows, int32_t dim,
-    int32_t k, const uint16_t *__restrict__ src, const uint32_t *__restrict__ allow_bits) {
+//
+// QP, queries per pass ("K1F8 pair pass").  QP == 1: one query per walk of the wave's row block, its codes
+// in registers (qv).  QP == 2: queries qi and qi + 1 share one walk -- every batch is loaded once and reduced twice, so
+// a pair reads the image once.  The wave waits out its loads for more than half of an iteration, which is where the
+// second query's dot products, bounds and offer go.  A second qv does not fit under 128 VGPRs: both queries' codes
+// live in LDS instead, each lane's own CH dwordx4 per query (a register file extension: written in next_query, read
+// back by the same lane with one ds_read_b128 per chunk and batch -- no cross-lane traffic, no barrier; LDS reads
+// count in lgkmcnt, so the counted vmcnt waits on the batches stay what they were).  Per query nothing changes: the same
+// integer chain, gather, bounds, hi placement and offers in the same order, hence the same bits everywhere.
+template <int G, int CH, int R, bool FILTER, int QP>
+__device__ __forceinline__ void i8_scan_body(const i32x4 *__restrict__ img, const f32x4 *__restrict__ meta,
+                                             const PrefilterQueries Q, int64_t n_rows, int32_t dim, int32_t k,
+                                             const uint16_t *__restrict__ src, const uint32_t *__restrict__ allow_bits) {
     constexpr int GROUPS = kWave / G;
     constexpr int RW = GROUPS * R;
     static_assert(RW <= kWave, "a batch's rows fit the lanes of one wave");
+    static_assert(QP == 1 || QP == 2, "one or two queries per pass");
     constexpr int WAVES = kScanWaves;
     __shared__ uint32_t lds_allow[FILTER ? 2048 : 1];
+    __shared__ i32x4 lds_q[QP == 2 ? WAVES * QP * CH * kWave : 1];  // [wave][query][chunk][lane]
 
     const int lane = lane_id();
-    const int wave = threadIdx.x / kWave;
+    // QP == 2: the wave index as a scalar, so that the walk (base, lim, hbase, the query index and with it the loads of
+    // the queries' pointers) stays in SGPRs and s_loads; QP == 1 keeps the code it had
+    const int wave = QP == 2 ? __builtin_amdgcn_readfirstlane(threadIdx.x / kWave) : threadIdx.x / kWave;
     const int sub = lane % G, grp = lane / G;
     if constexpr (FILTER) {
         for (int i = threadIdx.x; i < 2048; i += kScanThreads) lds_allow[i] = allow_bits[i];
@@ -398,80 +411,94 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(4)
     }
     const int64_t row_i4 = dim / 16;
     const float eta = prefilter_eta(dim);
-    int32_t qv[CH][4];  // this lane's query codes, 4 per dword (the image's byte order)
-    float sq = 1.f, qn = 0.f, eqn = 0.f;
-    WaveTopK<float> top;
+    int32_t qv[QP == 1 ? CH : 1][4];  // QP == 1: this lane's query codes, 4 per dword (the image's byte order)
+    float sq[QP], qn[QP], eqn[QP];
+    WaveTopK<float> top[QP];
     struct Batch {
         i32x4 v[R][CH];
         f32x4 m;  // {s_e, m1, m2, -} of row base + lane
         uint32_t sid;
     };
     auto next_query = [&](int32_t qi) {
-        const f32x4 *__restrict__ query = reinterpret_cast<const f32x4 *>(Q.q[qi]);
-        double ss = 0.0;
-        float mx = 0.f;
 #pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            // one chunk (16 floats) in registers at a time, beside the batch in flight; the second pass reads the
-            // slice again (L2 hits) -- the fences keep the compiler from merging or hoisting the loads
-            asm volatile("" ::: "memory");
+        for (int p = 0; p < QP; ++p) {
+            const f32x4 *__restrict__ query = reinterpret_cast<const f32x4 *>(Q.q[qi + p]);
+            double ss = 0.0;
+            float mx = 0.f;
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const f32x4 x = query[4 * (c * G + sub) + t];
+            for (int c = 0; c < CH; ++c) {
+                // one chunk (16 floats) in registers at a time, beside the batch in flight; the second pass reads the
+                // slice again (L2 hits) -- the fences keep the compiler from merging or hoisting the loads
+                asm volatile("" ::: "memory");
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    ss += (double)x[j] * (double)x[j];
-                    mx = __builtin_fmaxf(mx, __builtin_fabsf(x[j]));
+                for (int t = 0; t < 4; ++t) {
+                    const f32x4 x = query[4 * (c * G + sub) + t];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        ss += (double)x[j] * (double)x[j];
+                        mx = __builtin_fmaxf(mx, __builtin_fabsf(x[j]));
+                    }
                 }
             }
-        }
 #pragma unroll
-        for (int off = 1; off < G; off <<= 1) {
-            ss += __shfl_xor(ss, off, kWave);
-            mx = __builtin_fmaxf(mx, __shfl_xor(mx, off, kWave));
-        }
-        sq = i8_scale(mx);
-        const float inv = 1.f / sq;
-        double d2 = 0.0;
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const f32x4 x = query[4 * (c * G + sub) + t];
-                uint32_t b = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float y = quantise(x[j], inv);
-                    const double d = (double)x[j] - (double)sq * (double)y;
-                    d2 += d * d;
-                    b |= pack_i8(y, j);
-                }
-                qv[c][t] = (int32_t)b;
+            for (int off = 1; off < G; off <<= 1) {
+                ss += __shfl_xor(ss, off, kWave);
+                mx = __builtin_fmaxf(mx, __shfl_xor(mx, off, kWave));
             }
-        }
+            sq[p] = i8_scale(mx);
+            const float inv = 1.f / sq[p];
+            double d2 = 0.0;
 #pragma unroll
-        for (int off = 1; off < G; off <<= 1) d2 += __shfl_xor(d2, off, kWave);
-        const double nq = __builtin_sqrt(ss) * (1.0 + 0x1p-30), ne = __builtin_sqrt(d2) * (1.0 + 0x1p-30);
-        qn = nq <= kRadiusCap ? __double2float_ru(nq) : __builtin_huge_valf();  // NaN / inf / huge: +inf
-        eqn = ne <= kRadiusCap ? __double2float_ru(ne) : __builtin_huge_valf();
-        sq = read_lane(sq, 0);  // equal in every lane: held in SGPRs
-        qn = read_lane(qn, 0);
-        eqn = read_lane(eqn, 0);
-        top.init(k);
+            for (int c = 0; c < CH; ++c) {
+                asm volatile("" ::: "memory");
+                i32x4 codes;  // QP == 2: this lane's chunk, on its way to LDS
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const f32x4 x = query[4 * (c * G + sub) + t];
+                    uint32_t b = 0;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float y = quantise(x[j], inv);
+                        const double d = (double)x[j] - (double)sq[p] * (double)y;
+                        d2 += d * d;
+                        b |= pack_i8(y, j);
+                    }
+                    if constexpr (QP == 1) qv[c][t] = (int32_t)b;
+                    else codes[t] = (int32_t)b;
+                }
+                if constexpr (QP == 2) lds_q[((wave * QP + p) * CH + c) * kWave + lane] = codes;
+            }
+#pragma unroll
+            for (int off = 1; off < G; off <<= 1) d2 += __shfl_xor(d2, off, kWave);
+            const double nq = __builtin_sqrt(ss) * (1.0 + 0x1p-30), ne = __builtin_sqrt(d2) * (1.0 + 0x1p-30);
+            qn[p] = nq <= kRadiusCap ? __double2float_ru(nq) : __builtin_huge_valf();  // NaN / inf / huge: +inf
+            eqn[p] = ne <= kRadiusCap ? __double2float_ru(ne) : __builtin_huge_valf();
+            sq[p] = read_lane(sq[p], 0);  // equal in every lane: held in SGPRs
+            qn[p] = read_lane(qn[p], 0);
+            eqn[p] = read_lane(eqn[p], 0);
+            top[p].init(k);
+        }
     };
     const int64_t total_waves = (int64_t)gridDim.x * WAVES;
     const int64_t wave_global = (int64_t)blockIdx.x * WAVES + wave;
     const int64_t rows_per_wave = ((n_rows + total_waves - 1) / total_waves + RW - 1) / RW * RW;
     const int64_t base0 = wave_global * rows_per_wave;
     const int64_t lim = base0 + rows_per_wave < n_rows ? base0 + rows_per_wave : n_rows;
-    float hb = 0.f;  // lane j <- hi of row hbase + j
+    float hb[QP];  // lane j <- hi of row hbase + j (both queries of a pair are at the same row)
+#pragma unroll
+    for (int p = 0; p < QP; ++p) {
+        sq[p] = 1.f;
+        qn[p] = eqn[p] = hb[p] = 0.f;
+    }
     int64_t hbase = base0;
     int32_t qi = 0;
     auto flush = [&](int32_t qe) {
-        Q.blk_s[qe][(blockIdx.x * WAVES + wave) * kListLen + lane] = top.s;
-        Q.blk_r[qe][(blockIdx.x * WAVES + wave) * kListLen + lane] = top.r;
-        if (hbase + lane < lim) Q.hi[qe][hbase + lane] = hb;
+#pragma unroll
+        for (int p = 0; p < QP; ++p) {
+            Q.blk_s[qe + p][(blockIdx.x * WAVES + wave) * kListLen + lane] = top[p].s;
+            Q.blk_r[qe + p][(blockIdx.x * WAVES + wave) * kListLen + lane] = top[p].r;
+            if (hbase + lane < lim) Q.hi[qe + p][hbase + lane] = hb[p];
+        }
         hbase = base0;
     };
     // addresses: a wave-uniform 64-bit base and 32-bit lane offsets (rows past the end clamp to the last row)
@@ -493,45 +520,91 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(4)
         if constexpr (FILTER) bt.sid = src[base + mc];
     };
     auto reduce = [&](int64_t base, const Batch &bt) {
-        int32_t sum = 0;  // lane j < RW: v . u of row base + j
+        int32_t sum[QP];  // lane j < RW: v . u of row base + j
+        if constexpr (QP == 1) {
+            sum[0] = 0;
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            int32_t acc = 0;
+            for (int r = 0; r < R; ++r) {
+                int32_t acc = 0;
 #pragma unroll
-            for (int c = 0; c < CH; ++c)
+                for (int c = 0; c < CH; ++c)
 #pragma unroll
-                for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_sdot4(bt.v[r][c][t], qv[c][t], acc, false);
-            acc = group_sum_i32<G>(acc);
+                    for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_sdot4(bt.v[r][c][t], qv[c][t], acc, false);
+                acc = group_sum_i32<G>(acc);
 #pragma unroll
-            for (int g = 0; g < GROUPS; ++g) {
-                const int32_t sg = (int32_t)read_lane((uint32_t)acc, g * G + G - 1);
-                sum = lane == r * GROUPS + g ? sg : sum;
+                for (int g = 0; g < GROUPS; ++g) {
+                    const int32_t sg = (int32_t)read_lane((uint32_t)acc, g * G + G - 1);
+                    sum[0] = lane == r * GROUPS + g ? sg : sum[0];
+                }
+            }
+        } else {
+            // a chunk of both queries' codes from LDS, then every row of the batch against it: the same chain per
+            // (query, row) as above, c ascending, t ascending
+            int32_t acc[QP][R];
+#pragma unroll
+            for (int p = 0; p < QP; ++p)
+#pragma unroll
+                for (int r = 0; r < R; ++r) acc[p][r] = 0;
+            // the codes of chunk c + 1 are on their way from LDS while chunk c is multiplied (one wave per SIMD: nothing
+            // else would cover a ds_read's latency)
+            i32x4 qc[2][QP];
+#pragma unroll
+            for (int p = 0; p < QP; ++p) qc[0][p] = lds_q[((wave * QP + p) * CH + 0) * kWave + lane];
+#pragma unroll
+            for (int c = 0; c < CH; ++c) {
+                if (c + 1 < CH) {
+#pragma unroll
+                    for (int p = 0; p < QP; ++p) qc[(c + 1) & 1][p] = lds_q[((wave * QP + p) * CH + c + 1) * kWave + lane];
+                }
+#pragma unroll
+                for (int p = 0; p < QP; ++p)
+#pragma unroll
+                    for (int r = 0; r < R; ++r)
+#pragma unroll
+                        for (int t = 0; t < 4; ++t)
+                            acc[p][r] = __builtin_amdgcn_sdot4(bt.v[r][c][t], qc[c & 1][p][t], acc[p][r], false);
+            }
+#pragma unroll
+            for (int p = 0; p < QP; ++p) {
+                sum[p] = 0;
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const int32_t a = group_sum_i32<G>(acc[p][r]);
+#pragma unroll
+                    for (int g = 0; g < GROUPS; ++g) {
+                        const int32_t sg = (int32_t)read_lane((uint32_t)a, g * G + G - 1);
+                        sum[p] = lane == r * GROUPS + g ? sg : sum[p];
+                    }
+                }
             }
         }
         const int64_t row = base + lane;
         bool ok = lane < RW && row < lim;
         if constexpr (FILTER) ok = ok && source_ok(lds_allow, bt.sid);
-        const float a = (float)sum * (sq * bt.m.x);
-        float lo, hi;
-        row_bounds_i8(a, bt.m.y, bt.m.z, qn, eqn, eta, lo, hi);
-        const float hv = ok ? hi : __builtin_nanf("");
         // rows base .. base + RW - 1 take slots off .. off + RW - 1 of the 64-row store, the overflow the next one's
-        const int off = (int)(base - hbase);
-        const float sh = __shfl(hv, (lane - off) & (kWave - 1), kWave);
-        if (lane >= off && lane < off + RW) hb = sh;
-        if (off + RW >= kWave) {
-            if (hbase + lane < lim) Q.hi[qi][hbase + lane] = hb;
-            hbase += kWave;
-            if (lane < off + RW - kWave) hb = sh;
+#pragma unroll
+        for (int p = 0; p < QP; ++p) {
+            const float a = (float)sum[p] * (sq[p] * bt.m.x);
+            float lo, hi;
+            row_bounds_i8(a, bt.m.y, bt.m.z, qn[p], eqn[p], eta, lo, hi);
+            const float hv = ok ? hi : __builtin_nanf("");
+            const int off = (int)(base - hbase);
+            const float sh = __shfl(hv, (lane - off) & (kWave - 1), kWave);
+            if (lane >= off && lane < off + RW) hb[p] = sh;
+            if (off + RW >= kWave) {
+                if (hbase + lane < lim) Q.hi[qi + p][hbase + lane] = hb[p];
+                if (p == QP - 1) hbase += kWave;  // (both queries of a pair store at the same batch)
+                if (lane < off + RW - kWave) hb[p] = sh;
+            }
+            const uint32_t r32 = (uint32_t)row;
+            top[p].offer_lanes(ok && top[p].admits(lo, r32), lo, r32);
         }
-        const uint32_t r32 = (uint32_t)row;
-        top.offer_lanes(ok && top.admits(lo, r32), lo, r32);
     };
     if (base0 >= n_rows) {  // a wave without rows (tiny corpora): empty lists
-        top.init(1);
+        top[0].init(1);
         for (int32_t qe = 0; qe < Q.n; ++qe) {
-            Q.blk_s[qe][(blockIdx.x * WAVES + wave) * kListLen + lane] = top.s;
-            Q.blk_r[qe][(blockIdx.x * WAVES + wave) * kListLen + lane] = top.r;
+            Q.blk_s[qe][(blockIdx.x * WAVES + wave) * kListLen + lane] = top[0].s;
+            Q.blk_r[qe][(blockIdx.x * WAVES + wave) * kListLen + lane] = top[0].r;
         }
         return;
     }
@@ -539,13 +612,14 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(4)
     issue(base0, b0);  // in flight during the first prologue
     next_query(0);
     int64_t base = base0;
-    // K1's loop: the next batch is issued unconditionally before the current one is reduced (dense_scan.hip)
+    // K1's loop: the next batch is issued unconditionally before the current one is reduced (dense_scan.hip); after the
+    // last batch of a pass the walk wraps to the block's first row for the next QP queries (Q.n is a multiple of QP)
     for (;;) {
         int32_t nq = qi;
         int64_t next = base + RW;
         if (next >= lim) {
             next = base0;
-            ++nq;
+            nq += QP;
         }
         issue(next, b1);
         reduce(base, b0);
@@ -559,7 +633,7 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(4)
         next = base + RW;
         if (next >= lim) {
             next = base0;
-            ++nq;
+            nq += QP;
         }
         issue(next, b0);
         reduce(base, b1);
@@ -571,6 +645,21 @@ __global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(4)
         }
         base = next;
     }
+}
+
+template <int G, int CH, int R, bool FILTER>
+__global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(4))) void dense_prefilter_i8_scan_kernel(
+    const i32x4 *__restrict__ img, const f32x4 *__restrict__ meta, PrefilterQueries Q, int64_t n_rows, int32_t dim,
+    int32_t k, const uint16_t *__restrict__ src, const uint32_t *__restrict__ allow_bits) {
+    i8_scan_body<G, CH, R, FILTER, 1>(img, meta, Q, n_rows, dim, k, src, allow_bits);
+}
+
+// the pair pass: Q.n is even (launch_dense_prefilter_scan sends an odd last query through the kernel above)
+template <int G, int CH, int R, bool FILTER>
+__global__ __launch_bounds__(kScanThreads) __attribute__((amdgpu_waves_per_eu(4))) void dense_prefilter_i8_pair_kernel(
+    const i32x4 *__restrict__ img, const f32x4 *__restrict__ meta, PrefilterQueries Q, int64_t n_rows, int32_t dim,
+    int32_t k, const uint16_t *__restrict__ src, const uint32_t *__restrict__ allow_bits) {
+    i8_scan_body<G, CH, R, FILTER, 2>(img, meta, Q, n_rows, dim, k, src, allow_bits);
 }
 
 // ---------------------------------------------------------------- 2. T per query: one workgroup of 16 waves each
@@ -824,6 +913,41 @@ static PrefilterQueries prefilter_queries(const anrag_index *idx, const float *c
     return Q;
 }
 
+// The shapes with a pair instantiation of the int8 scan (dense_prefilter_i8_pair_kernel): every one that stays within 128
+// VGPRs without spills.  A shape that is not listed keeps single passes for every query of a group.
+template <int G, int CH, bool FILTER>
+constexpr bool i8_pair_shape() {
+    return true;
+}
+
+bool dense_prefilter_pairs(const anrag_index *idx, bool filtered) {
+    bool ok = false;
+    if (idx->pf_form != kPrefilterInt8) return false;
+    prefilter_dispatch(idx->dim, [&](auto ps) {
+        using Q4 = typename decltype(ps)::Quarter;
+        ok = filtered ? i8_pair_shape<Q4::kG, Q4::kCH, true>() : i8_pair_shape<Q4::kG, Q4::kCH, false>();
+    });
+    return ok;
+}
+
+// the queries [first, first + n) of Q as a group of their own
+static PrefilterQueries prefilter_queries_slice(const PrefilterQueries &Q, int first, int n) {
+    PrefilterQueries S;
+    S.n = n;
+    for (int i = 0; i < kScanGroupMax; ++i) {
+        const int j = first + (i < n ? i : 0);
+        S.q[i] = Q.q[j];
+        S.hi[i] = Q.hi[j];
+        S.blk_s[i] = Q.blk_s[j];
+        S.blk_r[i] = Q.blk_r[j];
+        S.thr[i] = Q.thr[j];
+    }
+    return S;
+}
+
+// The int8 form takes the queries of a group two at a time through one walk of the image (the pair kernel) wherever the
+// shape has a pair instantiation and pairing is on; an odd last query follows in a launch of the single kernel on the
+// same stream (a run-time branch into the single code inside the pair kernel would hold both forms' registers).
 int launch_dense_prefilter_scan(anrag_index *idx, hipStream_t st, const float *const *d_queries, int32_t n_queries,
                                 int32_t k, const uint32_t *allow, const int *sets) {
     const PrefilterQueries Q = prefilter_queries(idx, d_queries, n_queries, sets);
@@ -834,12 +958,32 @@ int launch_dense_prefilter_scan(anrag_index *idx, hipStream_t st, const float *c
         if (idx->pf_form == kPrefilterInt8) {
             const i32x4 *img = reinterpret_cast<const i32x4 *>(idx->d_pf_img);
             const f32x4 *meta = reinterpret_cast<const f32x4 *>(idx->d_pf_m);
+            const uint16_t *src = allow ? idx->d_dense_src : nullptr;
+            int32_t paired = 0;  // queries taken by the pair kernel
+            if (idx->scan_pair_mode != 0 && n_queries >= 2) {
+                if constexpr (i8_pair_shape<Q4::kG, Q4::kCH, true>())
+                    if (allow) {
+                        paired = n_queries & ~1;
+                        dense_prefilter_i8_pair_kernel<Q4::kG, Q4::kCH, Q4::kR, true><<<grid, kScanThreads, 0, st>>>(
+                            img, meta, prefilter_queries_slice(Q, 0, paired), idx->n_rows, idx->dim, k, src, allow);
+                    }
+                if constexpr (i8_pair_shape<Q4::kG, Q4::kCH, false>())
+                    if (!allow) {
+                        paired = n_queries & ~1;
+                        dense_prefilter_i8_pair_kernel<Q4::kG, Q4::kCH, Q4::kR, false><<<grid, kScanThreads, 0, st>>>(
+                            img, meta, prefilter_queries_slice(Q, 0, paired), idx->n_rows, idx->dim, k, src, allow);
+                    }
+            }
+            idx->pf_pair_passes += paired / 2;
+            idx->pf_single_passes += n_queries - paired;
+            if (paired == n_queries) return;
+            const PrefilterQueries S = paired ? prefilter_queries_slice(Q, paired, n_queries - paired) : Q;
             if (allow)
                 dense_prefilter_i8_scan_kernel<Q4::kG, Q4::kCH, Q4::kR, true><<<grid, kScanThreads, 0, st>>>(
-                    img, meta, Q, idx->n_rows, idx->dim, k, idx->d_dense_src, allow);
+                    img, meta, S, idx->n_rows, idx->dim, k, src, allow);
             else
                 dense_prefilter_i8_scan_kernel<Q4::kG, Q4::kCH, Q4::kR, false><<<grid, kScanThreads, 0, st>>>(
-                    img, meta, Q, idx->n_rows, idx->dim, k, nullptr, nullptr);
+                    img, meta, S, idx->n_rows, idx->dim, k, nullptr, nullptr);
         } else {
             const f32x4 *img = reinterpret_cast<const f32x4 *>(idx->d_pf_img);
             if (allow)

@@ -562,6 +562,17 @@ class Index:
         nat.check(self._lib.anrag_dense_prefilter_stats(self.handle, C.byref(q), C.byref(s)))
         return q.value, s.value
 
+    def set_scan_pairing(self, mode: int) -> None:
+        """The int8 prefilter's pair pass and the pairing of single `hybrid_search_device` calls
+        (`anrag_set_scan_pairing`): 0 off, 1 auto (default), 2 always hold a lone query for a partner (tests)."""
+        nat.check(self._lib.anrag_set_scan_pairing(self.handle, int(mode)))
+
+    def scan_pair_stats(self) -> tuple:
+        """(pair passes, single passes, pending) of the int8 scan (`anrag_scan_pair_stats`); launches nothing."""
+        a, b, p = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        nat.check(self._lib.anrag_scan_pair_stats(self.handle, C.byref(a), C.byref(b), C.byref(p)))
+        return a.value, b.value, p.value
+
     def debug_prefilter_read(self, data: bool = True) -> dict:
         """The prefilter as built (`anrag_debug_prefilter_read`): form (0 off, 1 fp16, 2 int8), rows_per_wave and
         batch_rows of the scan and, with `data`, image ([n, d] float16 / int8) and meta ([n] / [n, 4] float32)."""

@@ -249,6 +249,21 @@ int anrag_set_dense_prefilter(anrag_index *idx, int32_t mode);
  * (waits for the index's streams). */
 int anrag_dense_prefilter_stats(anrag_index *idx, int64_t *queries, int64_t *survivors);
 
+/* The int8 prefilter's pair pass: two queued queries share one walk of the shadow image (half the bytes per query; every
+ * value written per query is the single pass's, bit for bit).  Groups of queries (anrag_hybrid_candidates_group_device,
+ * anrag_dense_search_device with n_queries > 1, the per-query branch of anrag_hybrid_search_batch, shard groups) take it
+ * two at a time, an odd last query a single pass.  mode: 0 off (single passes only, nothing is ever held), 1 (default)
+ * on, and single anrag_hybrid_search_device calls pair by the launch rule given there, 2 as 1 but a lone
+ * anrag_hybrid_search_device query is ALWAYS held until a partner or a flushing call arrives (deterministic: for tests).
+ * The answers never depend on it.  The environment variable ANRAG_SCAN_PAIR=0|1|2, read at anrag_index_create, sets the
+ * initial mode. */
+int anrag_set_scan_pairing(anrag_index *idx, int32_t mode);
+
+/* Cumulative int8 scan passes over the image by form -- a pair pass serves two queries, a single pass one -- and whether
+ * a query is held at this moment (1 or 0).  Reads without launching the held query and without waiting; NULL outputs are
+ * skipped. */
+int anrag_scan_pair_stats(anrag_index *idx, int64_t *pair_passes, int64_t *single_passes, int32_t *pending);
+
 /* All N scores of one query (what search_engine.py:81 materialises), for tests
  * and for callers that post-process scores themselves.  out: host, n_rows fp32. */
 int anrag_dense_scores(anrag_index *idx, const float *query, float *out_scores);
@@ -348,7 +363,23 @@ int anrag_hybrid_search_f64(anrag_index *idx, const double *query, const int32_t
  * on the device) until the query 32 back has finished with its buffers.
  * A corpus of at most 1 GiB on the index's own streams takes another route: the query's three launches go back to back on
  * ONE of four lane streams (no events between them) and consecutive queries rotate over the lanes (the reference's own corpus,
- * 9,609 x 384: 17 instead of 43 us per query); results are then complete behind anrag_index_sync / anrag_index_signal_stream. */
+ * 9,609 x 384: 17 instead of 43 us per query); results are then complete behind anrag_index_sync / anrag_index_signal_stream.
+ * PAIRING (anrag_set_scan_pairing).  Where the int8 prefilter answers the dense leg on the pipeline route and the index
+ * runs on its own three streams, the call may return ANRAG_OK with the query HELD, not yet launched: the int8 scan takes
+ * two queries through one walk of the shadow image, so two consecutive calls with the same similarity_k, weights, wrrf_k,
+ * top_n and allow pointers are launched together as one group of 2.  The launch rule, per call:
+ *   1. a query is held and the parameters are identical: both are launched as a group;
+ *   2. a query is held and the parameters differ: the held one is launched alone, then 3;
+ *   3. the latest scan launched on the index has not finished: this query is held (nothing launched now would start
+ *      before that scan ends);
+ *   4. otherwise the query is launched alone: one query on an idle device is never held.
+ * A held query is launched by the next call of ANY other entry point that takes the index (anrag_index_sync,
+ * anrag_index_signal_stream, anrag_index_wait_stream, anrag_index_set_streams, loads, searches, anrag_rank_batch, the
+ * debug and profile calls, anrag_index_destroy), before that call does anything else; an error of that launch is returned
+ * by that call.  Results on the index's own streams can only be observed through anrag_index_sync,
+ * anrag_index_signal_stream or a host-pointer call, so a query is on the device no later than the first call that could
+ * see its answer.  Operands must stay valid until then, as they must until the kernels have run.  With caller-owned
+ * streams (anrag_index_set_streams) nothing is ever held. */
 int anrag_hybrid_search_device(anrag_index *idx, const float *d_query, const int32_t *d_term_ids,
                                int32_t n_terms, int32_t similarity_k, double w_dense,
                                double w_bm25, double wrrf_k, int32_t top_n,

@@ -16,7 +16,7 @@ import statistics as st
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("trace")
-    ap.add_argument("--scan", default=r"dense_prefilter(_i8)?_scan_kernel")
+    ap.add_argument("--scan", default=r"dense_prefilter(_i8)?_(scan|pair)_kernel")
     ap.add_argument("--keep", type=int, default=0)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
