@@ -110,6 +110,7 @@ _SIGNATURES = {
     "anrag_profile_read_units": [_p, C.c_int, C.POINTER(_i64)],
     "anrag_index_info": [_p, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
     "anrag_debug_alloc_calls": [C.POINTER(_i64)],
+    "anrag_debug_bm25_geometry": [_p, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)],
     "anrag_debug_prefilter_read": [_p, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i32), _p, _p],
     "anrag_debug_prefilter_bounds": [_p, _p, _i32, _i32, _p, _i32, C.c_uint32, _p, _p],
     "anrag_debug_prefilter_f64": [_p, _p, _p, C.POINTER(_f64), C.POINTER(_f64)],

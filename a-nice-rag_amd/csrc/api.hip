@@ -1776,6 +1776,18 @@ int anrag_debug_alloc_calls(int64_t *out_calls) {
     return ANRAG_OK;
 }
 
+int anrag_debug_bm25_geometry(anrag_index *idx, int32_t *out_n_cus, int32_t *out_part_docs, int32_t *out_n_parts,
+                              int32_t *out_form_single, int32_t *out_form_group) {
+    ANRAG_ENTER(idx);
+    const bool loaded = idx->d_post_doc != nullptr;
+    if (out_n_cus) *out_n_cus = idx->n_cus;
+    if (out_part_docs) *out_part_docs = loaded ? idx->part_docs : 0;
+    if (out_n_parts) *out_n_parts = loaded ? idx->n_parts : 0;
+    if (out_form_single) *out_form_single = loaded ? bm25_form(idx, 1) : 0;
+    if (out_form_group) *out_form_group = loaded ? bm25_form(idx, 2) : 0;
+    return ANRAG_OK;
+}
+
 int anrag_debug_prefilter_read(anrag_index *idx, int32_t *out_form, int64_t *out_rows_per_wave, int32_t *out_batch_rows,
                                void *out_image, float *out_meta) {
     ANRAG_ENTER(idx);

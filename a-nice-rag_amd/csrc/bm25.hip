@@ -692,6 +692,20 @@ int bm25_load(anrag_index *idx, const int64_t *indptr, int64_t n_terms, const in
     return ANRAG_OK;
 }
 
+// The kernel form a launch takes.  Partitions of <= 1,024 documents: the 256-thread form (one wave per SIMD, cheaper
+// barriers).  Larger ones: a query alone takes the 1,024-thread form (its 16 waves finish a partition soonest: 17.6
+// against 23.8 us per launch at 1M documents), a GROUP the 256-thread x 16-document form (two workgroups share a CU and a
+// quarter of the waves pay the per-wave overhead: 10.6 against 11.2 us per query at 8 queries per launch, 6.4 against
+// 8.6 for 2-term queries).  ANRAG_BM25_FORM=wide / tall forces one of them (measurements).
+static bool bm25_small_partitions(const anrag_index *idx) { return idx->part_docs <= kPostPerThread * kBm25ThreadsSmall; }
+
+int bm25_form(const anrag_index *idx, int32_t n_queries) {
+    if (bm25_small_partitions(idx)) return kBm25FormSmall;
+    static const int forced = [] { const char *e = getenv("ANRAG_BM25_FORM"); return !e ? 0 : (e[0] == 'w' ? 1 : (e[0] == 't' ? 2 : 0)); }();
+    const bool wide = forced == 1 || (forced == 0 && n_queries == 1);
+    return wide ? kBm25FormWide : kBm25FormTall;
+}
+
 // K3 only: per-partition lists (or every score) are left in HBM; the tail kernel finishes the top-k.
 // n <= kScanGroupMax queries in ONE launch: query i's lists into list set sets[i], or (d_scores_out given) its n_docs
 // scores to d_scores_out[i].
@@ -717,14 +731,7 @@ int launch_bm25_lists_group(anrag_index *idx, hipStream_t st, const int32_t *con
     }
     {
         LaunchTimer t(idx, ANRAG_KERNEL_BM25, st, n_queries);
-        // partitions of <= 1,024 documents: the 256-thread form (one wave per SIMD, cheaper barriers).  Larger ones: a
-        // query alone takes the 1,024-thread form (its 16 waves finish a partition soonest: 17.6 against 23.8 us per
-        // launch at 1M documents), a GROUP the 256-thread x 16-document form (two workgroups share a CU and a quarter
-        // of the waves pay the per-wave overhead: 10.6 against 11.2 us per query at 8 queries per launch, 6.4 against
-        // 8.6 for 2-term queries).  ANRAG_BM25_FORM=wide / tall forces one of them (measurements).
-        const bool small = idx->part_docs <= kPostPerThread * kBm25ThreadsSmall;
-        static const int forced = [] { const char *e = getenv("ANRAG_BM25_FORM"); return !e ? 0 : (e[0] == 'w' ? 1 : (e[0] == 't' ? 2 : 0)); }();
-        const bool wide = forced == 1 || (forced == 0 && n_queries == 1);
+        const int form = bm25_form(idx, n_queries);
         const dim3 grid((unsigned)idx->n_parts, (unsigned)n_queries);
 #define ANRAG_BM25_TG(F, S, T, D, G)                                                                              \
     do {                                                                                                          \
@@ -741,8 +748,8 @@ int launch_bm25_lists_group(anrag_index *idx, hipStream_t st, const int32_t *con
     } while (0)
 #define ANRAG_BM25(F, S)                                                                      \
     do {                                                                                      \
-        if (small) ANRAG_BM25_T(F, S, kBm25ThreadsSmall, kPostPerThread);                     \
-        else if (wide) ANRAG_BM25_T(F, S, kBm25Threads, kPostPerThread);                      \
+        if (form == kBm25FormSmall) ANRAG_BM25_T(F, S, kBm25ThreadsSmall, kPostPerThread);    \
+        else if (form == kBm25FormWide) ANRAG_BM25_T(F, S, kBm25Threads, kPostPerThread);     \
         else ANRAG_BM25_T(F, S, kBm25ThreadsSmall, kDocsPerThreadTall);                       \
     } while (0)
         if (d_scores_out) {
@@ -773,7 +780,7 @@ int launch_bm25_scores_table(anrag_index *idx, hipStream_t st, const int32_t *d_
     Q.terms_base = d_terms_base;
     Q.scores_base = d_scores_base;
     Q.scores_stride = scores_stride;
-    const bool small = idx->part_docs <= kPostPerThread * kBm25ThreadsSmall;
+    const bool small = bm25_small_partitions(idx);
     const dim3 grid((unsigned)idx->n_parts, (unsigned)n_queries);
     int rc;
     LaunchTimer t(idx, ANRAG_KERNEL_BM25, st, n_queries);

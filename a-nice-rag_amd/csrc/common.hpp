@@ -392,6 +392,9 @@ int launch_dense_scan_finish(anrag_index *idx, hipStream_t stream, const float *
                              int32_t k, const int *sets);
 int launch_bm25_lists(anrag_index *idx, hipStream_t st, const int32_t *d_terms, int32_t n_terms, int32_t k,
                       const uint32_t *d_allow_bits, double *d_scores_out, int set);
+// the K3 kernel form a launch of n_queries queries takes on this index (bm25.hip; anrag_debug_bm25_geometry reports it)
+enum { kBm25FormSmall = 0, kBm25FormWide = 1, kBm25FormTall = 2 };  // <256,4>, <1024,4>, <256,16>
+int bm25_form(const anrag_index *idx, int32_t n_queries);
 int launch_bm25_lists_group(anrag_index *idx, hipStream_t st, const int32_t *const *d_terms, const int32_t *n_terms,
                             int32_t n_queries, int32_t k, const uint32_t *d_allow_bits, double *const *d_scores_out,
                             const int *sets);

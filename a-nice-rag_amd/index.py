@@ -690,6 +690,54 @@ class Index:
                                               out.ctypes.data))
         return out
 
+    def bm25_geometry(self) -> dict:
+        """How K3 cuts and serves the loaded corpus (`anrag_debug_bm25_geometry`): n_cus, part_docs, n_parts and the
+        kernel form of a one-query launch / of a group launch (0 = 256 threads x 4 documents, 1 = 1,024 x 4 "wide",
+        2 = 256 x 16 "tall").  Without BM25 data everything but n_cus is 0."""
+        v = [C.c_int32() for _ in range(5)]
+        nat.check(self._lib.anrag_debug_bm25_geometry(self.handle, *[C.byref(x) for x in v]))
+        return dict(zip(("n_cus", "part_docs", "n_parts", "form_single", "form_group"), (x.value for x in v)))
+
+    def bm25_search_group(self, term_lists: Sequence[Sequence[int]], k: int, allow_source=None):
+        """Many BM25 queries in one call over `anrag_bm25_search_group_device` (16 queries per K3 launch, 1 <= k <= 64).
+        -> (doc [nq, k] int64 (-1 padded), score [nq, k] float64 (-inf padded), count [nq] int32); row i equals
+        `bm25_search(term_lists[i], k, allow_source)`.  A source filter needs the source ids given to `bm25_load`."""
+        nq, k = len(term_lists), int(k)
+        assert nq >= 1
+        lens = np.ascontiguousarray([len(t) for t in term_lists], dtype=np.int32)
+        off = np.zeros(nq + 1, dtype=np.int64)
+        np.cumsum(lens, out=off[1:])
+        terms = (np.concatenate([np.asarray(t, dtype=np.int32).reshape(-1) for t in term_lists]).astype(np.int32)
+                 if off[-1] else np.zeros(1, np.int32))
+        bufs = []
+        try:
+            d_terms = self.device_alloc(terms.nbytes)
+            bufs.append(d_terms)
+            d_out = self.device_alloc(nq * k * nat.CANDIDATE_DTYPE.itemsize)
+            bufs.append(d_out)
+            self.to_device(d_terms, terms)
+            d_allow = None
+            if allow_source is not None:
+                allow = np.flatnonzero(np.ascontiguousarray(allow_source, dtype=np.uint8))
+                assert allow.size == 0 or allow[-1] < 65536
+                bits = np.zeros(2048, dtype=np.uint32)  # bit s of word s / 32 = source s allowed
+                np.bitwise_or.at(bits, allow >> 5, np.uint32(1) << (allow & 31).astype(np.uint32))
+                d_allow = self.device_alloc(bits.nbytes)
+                bufs.append(d_allow)
+                self.to_device(d_allow, bits)
+            p_terms = (C.c_void_p * nq)(*[d_terms + 4 * int(o) for o in off[:nq]])
+            p_out = (C.c_void_p * nq)(*[d_out + i * k * nat.CANDIDATE_DTYPE.itemsize for i in range(nq)])
+            nat.check(self._lib.anrag_bm25_search_group_device(self.handle, p_terms, lens.ctypes.data, nq, k, d_allow, p_out))
+            self.sync()
+            rec = np.empty((nq, k), dtype=nat.CANDIDATE_DTYPE)
+            self.to_host(rec, d_out)
+        finally:
+            self.sync()
+            for b in bufs:
+                self.device_free(b)
+        doc = np.ascontiguousarray(rec["doc"])
+        return doc, np.ascontiguousarray(rec["score"]), (doc >= 0).sum(axis=1).astype(np.int32)
+
     # ------------------------------------------------------------------ fusion
     def wrrf(self, lists: Sequence[Sequence[int]], weights: Sequence[float], k: float, top_n: int):
         """-> (id [m] int64, score [m] float64), m = min(top_n, distinct ids)."""

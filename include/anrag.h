@@ -566,6 +566,13 @@ int anrag_index_info(anrag_index *idx, int64_t *dense_rows, int32_t *dense_dim,
 /* Device / pinned-host allocations and releases the library has made so far (process-wide; each one
  * synchronises the device).  A steady-state query loop must not move it: tests/test_gpu_no_alloc.py. */
 int anrag_debug_alloc_calls(int64_t *out_calls);
+/* How K3 cuts and serves the loaded BM25 corpus, for tests that aim at one kernel form (tests/test_gpu_bm25_forms.py).
+ * Read-only, no wait.  n_cus: the device's compute units; part_docs / n_parts: documents per partition (the last one may
+ * be shorter) and their number; form_single / form_group: the kernel form a launch of one query / of several takes,
+ * 0 = 256 threads x 4 documents, 1 = 1,024 x 4 ("wide"), 2 = 256 x 16 ("tall").  Every pointer is nullable.  Without
+ * BM25 data n_cus is still reported and the rest is 0. */
+int anrag_debug_bm25_geometry(anrag_index *idx, int32_t *n_cus, int32_t *part_docs, int32_t *n_parts,
+                              int32_t *form_single, int32_t *form_group);
 /* The dense prefilter seen from outside, for tests of its score intervals (tests/test_gpu_dense_prefilter_bounds.py).
  * Both wait for the index's streams; neither allocates.
  * anrag_debug_prefilter_read: the form in use (0 off, 1 fp16, 2 int8), the scan's row geometry (a wave owns

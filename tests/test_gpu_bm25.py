@@ -66,6 +66,7 @@ def test_index_builder_matches_oracle_statistics(small, big):
     _, cref, cbi, _ = big
     assert np.array_equal(cbi.indptr, cref.indptr) and np.array_equal(cbi.post_doc, cref.post_doc)
     assert np.array_equal(cbi.post_tf, cref.post_tf) and np.array_equal(cbi.idf, cref.idf)
+    # terms of >= 1,024 postings (kFrequentDf, bm25.hip) carry a partition table; the bar here is twice that
     assert (np.diff(cbi.indptr) >= 2048).sum() > 5, "corpus must exercise the frequent-term partition tables"
 
 
@@ -174,9 +175,11 @@ def test_dense_large_k():
 
 
 def test_mid_size_partitions_vs_oracle():
-    """600k documents = partitions of 2,560 documents: the 1,024-thread form of K3 with partly filled lanes and a short
-    last partition, multi-term queries with a source filter, against the oracle's CSR scorer (bit-exact scores, exact
-    ranks).  (The fixtures above are <= 30k documents: partitions of 256, the 256-thread form.)"""
+    """600k documents = partitions of 2,560 documents: the 1,024-thread form of K3, which is the form of a launch of ONE
+    query (every call here is one; a group launch over such partitions takes the 256-thread x 16-document form:
+    tests/test_gpu_bm25_forms.py), with partly filled lanes and a short last partition, multi-term queries with a source
+    filter, against the oracle's CSR scorer (bit-exact scores, exact ranks).  (The fixtures above are <= 30k documents:
+    partitions of 256, the 256-thread form.)"""
     import torch
     from oracle import ref_bm25, ref_search
     from anrag import synth
