@@ -37,7 +37,7 @@ class Candidate(C.Structure):
 
 CANDIDATE_DTYPE = np.dtype([("score", "<f8"), ("doc", "<i8")])
 
-LEG_DENSE, LEG_BM25 = 0, 1
+LEG_DENSE, LEG_BM25, LEG_DENSE_F64 = 0, 1, 2
 
 
 class RankLeg(C.Structure):
@@ -117,6 +117,7 @@ _SIGNATURES = {
     "anrag_debug_dense_lists": [_p, _p, _i32, _i32, _p, _i32, C.c_uint32, C.c_uint32, C.POINTER(_i32), _p, _p],
     "anrag_rank_batch": [_p, _i32, _i32, _i32, _f64, _i32, _i64, _p, _p, _p, _p, _p],
     "anrag_rank_caps": [C.POINTER(_i32), C.POINTER(_i32)],
+    "anrag_rank_f64_tile_stats": [_p, C.POINTER(_i64), C.POINTER(_i64)],
     "anrag_set_rank_wide": [_i32],
     "anrag_rank_wide_stats": [C.POINTER(_i64), C.POINTER(_i64)],
     "anrag_rank_wide_gate": [_i32, _i32, _i32, C.POINTER(_i32)],

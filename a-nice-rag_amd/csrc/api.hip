@@ -683,6 +683,13 @@ int anrag_dense_f64_stats(anrag_index *idx, int64_t *scanned, int64_t *sorted) {
     return ANRAG_OK;
 }
 
+int anrag_rank_f64_tile_stats(anrag_index *idx, int64_t *tiled, int64_t *passed) {
+    ANRAG_ENTER(idx);
+    if (tiled) *tiled = idx->rank_f64_tiled;
+    if (passed) *passed = idx->rank_f64_passed;
+    return ANRAG_OK;
+}
+
 int anrag_set_dense_f64_prefilter(anrag_index *idx, int32_t on) {
     ANRAG_ENTER(idx);
     ANRAG_REQUIRE(on == 0 || on == 1, "on must be 0 (K1D for every fp64 query) or 1 (the shadow prefilter while a form is built)");

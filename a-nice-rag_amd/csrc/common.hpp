@@ -224,6 +224,7 @@ struct anrag_index {
     double *d_blk_score_f64q = nullptr;    // fp64-query list scan (K1D, dense_scan_f64.hip): ONE set [kMaxScanLists][kListLen]
     bool f64_scan_on = true;               // anrag_set_dense_f64_scan
     int64_t f64_scanned = 0, f64_sorted = 0;  // fp64 queries answered by K1D / by the score array + sort
+    int64_t rank_f64_tiled = 0, rank_f64_passed = 0;  // fp64 list queries scored by K1TD / by per-query score passes
     // the shadow prefilter for fp64 queries (K1FD, dense_prefilter_f64.hip): on while a prefilter form is built
     bool f64_pf_on = true;                 // anrag_set_dense_f64_prefilter
     bool f64_pf_ready = false;             // Emax computed for the loaded corpus (the first such query after a load)
@@ -356,6 +357,10 @@ constexpr int kTileLaunchMax = 128;  // queries one K1T launch carries (dense_ti
 int dense_tile_group_max(const anrag_index *idx);  // queries K1T holds in LDS at a time at this dimension (0: no tile kernel)
 int launch_dense_tile(anrag_index *idx, hipStream_t stream, const float *d_queries, int64_t q_stride, int32_t n_queries,
                       const uint32_t *d_allow_bits, float *d_scores_out, int64_t scores_stride);
+// K1TD, fp64 score tiles for lists of float64 queries (dense_tile_f64.hip): up to kTileLaunchMax queries per launch
+int dense_tile_f64_group_max(const anrag_index *idx);  // queries K1TD holds in LDS at a time (0: no tile kernel at this dimension)
+int launch_dense_tile_f64(anrag_index *idx, hipStream_t stream, const double *d_queries, int64_t q_stride, int32_t n_queries,
+                          const uint32_t *d_allow_bits, double *d_scores_out, int64_t scores_stride);
 bool dense_tile_mfma_has_shape(const anrag_index *idx);  // ... on the matrix cores (dense_tile_mfma.hip)
 int dense_tile_mfma_block_rows(const anrag_index *idx);   // rows per block of that kernel (score rows must hold whole blocks)
 int launch_dense_tile_mfma(anrag_index *idx, hipStream_t stream, const float *d_queries, int64_t q_stride, int32_t n_queries,

@@ -1439,7 +1439,8 @@ extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int3
     for (int l = 0; l < n_legs; ++l) {
         const anrag_rank_leg &g = legs[l];
         ANRAG_REQUIRE(g.idx != nullptr, "leg %d: index handle is NULL", l);
-        ANRAG_REQUIRE(g.kind == ANRAG_LEG_DENSE || g.kind == ANRAG_LEG_BM25, "leg %d: kind %d", l, g.kind);
+        ANRAG_REQUIRE(g.kind == ANRAG_LEG_DENSE || g.kind == ANRAG_LEG_BM25 || g.kind == ANRAG_LEG_DENSE_F64, "leg %d: kind %d", l,
+                      g.kind);
         ANRAG_REQUIRE(g.weight > 0.0 && g.weight < __builtin_huge_val(), "leg %d: weight must be positive and finite", l);
         if (device < 0) device = g.idx->device;
         ANRAG_REQUIRE(g.idx->device == device, "leg %d lives on device %d, leg 0 on device %d", l, g.idx->device, device);
@@ -1458,7 +1459,7 @@ extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int3
     }
     for (int l = 0; l < n_legs; ++l) {
         const anrag_rank_leg &g = legs[l];
-        if (g.kind == ANRAG_LEG_DENSE) {
+        if (g.kind == ANRAG_LEG_DENSE || g.kind == ANRAG_LEG_DENSE_F64) {
             ANRAG_REQUIRE(g.idx->d_emb != nullptr, "leg %d: dense ranking before anrag_dense_load", l);
             ANRAG_REQUIRE(g.queries != nullptr, "leg %d: queries is NULL", l);
             ANRAG_REQUIRE(!(g.allow_source && !g.idx->d_dense_src), "leg %d: a source filter needs source ids", l);
@@ -1504,11 +1505,12 @@ extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int3
     const int32_t out_n = fuse ? fuse_n : (int32_t)std::min<int64_t>(top_n, leg_k[0]);
     int64_t per_query = 0, fixed = 0;
     for (int l = 0; l < n_legs; ++l) {
-        const bool dense = legs[l].kind == ANRAG_LEG_DENSE;
+        const bool dense = legs[l].kind == ANRAG_LEG_DENSE, dense64 = legs[l].kind == ANRAG_LEG_DENSE_F64;
         const int64_t stride = (leg_rows[l] + 63) / 64 * 64;
         per_query += stride * (dense ? 4 : 8) + (int64_t)leg_k[l] * 4 + 256 + 4 + 4;
         if (!fuse) per_query += (int64_t)leg_k[l] * 8 + 256;
-        per_query += dense ? (int64_t)legs[l].idx->dim * 4 : 8;  // BM25: the query's offset into the chunk's terms
+        // BM25: the query's offset into the chunk's terms
+        per_query += dense ? (int64_t)legs[l].idx->dim * 4 : (dense64 ? (int64_t)legs[l].idx->dim * 8 : 8);
         fixed += 2048 * 4 + 256 + 8 + 256 + (legs[l].doc_of_row ? leg_rows[l] * 4 + 256 : 0);
     }
     if (fuse && !fuse_in_lds) per_query += id_space * 12 + 512 + (int64_t)fuse_n * 12 + 512 + 4;
@@ -1544,6 +1546,7 @@ extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int3
         uint32_t *allow = nullptr;
         int32_t *doc_of_row = nullptr;
         float *q = nullptr;
+        double *q64 = nullptr;  // ANRAG_LEG_DENSE_F64
         int32_t *terms = nullptr;
         int32_t *seg_k = nullptr;
         int64_t *term_off = nullptr;
@@ -1575,6 +1578,9 @@ extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int3
         if (dense) {
             ld[l].q = cv.take<float>(chunk * g.idx->dim);
             ld[l].scores = cv.take<float>(chunk * ld[l].stride);
+        } else if (g.kind == ANRAG_LEG_DENSE_F64) {
+            ld[l].q64 = cv.take<double>(chunk * g.idx->dim);
+            ld[l].scores = cv.take<double>(chunk * ld[l].stride);
         } else {
             ld[l].terms = cv.take<int32_t>(std::max<int64_t>(max_terms_chunk, 1));
             ld[l].seg_k = cv.take<int32_t>(chunk);
@@ -1678,6 +1684,30 @@ extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int3
                 else if ((rc = launch_seg_sort<float, false>(device, st, c, tile, ld[l].stride, nullptr, 0, (int32_t)leg_rows[l],
                                                              leg_k[l], nullptr, ld[l].rows, ld[l].row_keys, leg_k[l], ld[l].cnt,
                                                              wide)))
+                    return rc;
+            } else if (g.kind == ANRAG_LEG_DENSE_F64) {
+                // float64 queries: fp64 score tiles (K1TD, dense_tile_f64.hip), then the BM25 leg's path for an fp64 tile
+                ANRAG_HIP(hipMemcpyAsync(ld[l].q64, reinterpret_cast<const double *>(g.queries) + q0 * ix->dim,
+                                         (size_t)c * ix->dim * sizeof(double), hipMemcpyHostToDevice, st));
+                double *tile = static_cast<double *>(ld[l].scores);
+                const int tile_n = getenv("ANRAG_RANK_SCAN_TILES") ? 0 : dense_tile_f64_group_max(ix);
+                for (int32_t g0 = 0; tile_n > 0 && g0 < c; g0 += kTileLaunchMax)  // the rows once per group of queries
+                    if ((rc = launch_dense_tile_f64(ix, st, ld[l].q64 + (int64_t)g0 * ix->dim, ix->dim,
+                                                    std::min<int32_t>(kTileLaunchMax, c - g0), ld[l].allow,
+                                                    tile + (int64_t)g0 * ld[l].stride, ld[l].stride)))
+                        return rc;
+                for (int32_t q = tile_n > 0 ? c : 0; q < c; ++q)  // other dimensions: a score pass per query, same bits
+                    if ((rc = launch_dense_scores_f64(ix, st, ld[l].q64 + (int64_t)q * ix->dim, ld[l].allow,
+                                                      tile + (int64_t)q * ld[l].stride)))
+                        return rc;
+                (tile_n > 0 ? ix->rank_f64_tiled : ix->rank_f64_passed) += c;
+                if (count_only)
+                    rank_count_kernel<double><<<c, kRankThreads, 0, st>>>(tile, ld[l].stride, (int32_t)leg_rows[l], leg_k[l],
+                                                                         nullptr, ld[l].doc_of_row, out_n, d_expect, d_rank,
+                                                                         d_out_cnt);
+                else if ((rc = launch_seg_sort<double, false>(device, st, c, tile, ld[l].stride, nullptr, 0,
+                                                              (int32_t)leg_rows[l], leg_k[l], nullptr, ld[l].rows,
+                                                              ld[l].row_keys, leg_k[l], ld[l].cnt, wide)))
                     return rc;
             } else {
                 const int64_t t0 = g.term_offsets[q0];

@@ -91,7 +91,17 @@ def _fill_leg(slot, leg: dict, i: int, n_queries: int, keep: list) -> None:
         dmap = np.ascontiguousarray(dmap, dtype=np.int64)
         keep.append(dmap)
     slot.doc_of_row = nat.ptr(dmap)
-    if leg.get("queries") is not None:
+    if leg.get("queries_f64") is not None:
+        q = np.ascontiguousarray(leg["queries_f64"])
+        assert q.dtype == np.float64, f"leg {i}: queries_f64 must be float64 (got {q.dtype}); it is never cast"
+        assert leg.get("queries") is None, f"leg {i}: queries and queries_f64 are two kinds of leg"
+        if q.ndim == 1:
+            q = q[None, :]
+        assert q.shape == (n_queries, ix.dim), f"leg {i}: queries_f64 {q.shape} != ({n_queries}, {ix.dim})"
+        keep.append(q)
+        slot.kind = nat.LEG_DENSE_F64
+        slot.queries = q.ctypes.data
+    elif leg.get("queries") is not None:
         q = _f32(leg["queries"])
         if q.ndim == 1:
             q = q[None, :]
@@ -138,8 +148,10 @@ def rank_batch(legs: Sequence[dict], n_queries: int, similarity_k: int, wrrf_k: 
                id_space: int = 0, want_scores: bool = False, expect=None, want_ids: bool = True):
     """`anrag_rank_batch`: full-ranking retrieval (large k) for a LIST of queries, every step on the device.
     `legs`: dicts in the reference's list order (dense models first, BM25 last) with
-        index (Index), weight, allow (uint8 per source or None), doc_of_row (int64 per row or None), and either
-        queries (float32 [nq, dim]) or term_lists (one int32 sequence per query; an empty one = no BM25 for that query).
+        index (Index), weight, allow (uint8 per source or None), doc_of_row (int64 per row or None), and one of
+        queries (float32 [nq, dim]; any other dtype is cast to float32), queries_f64 (float64 [nq, dim], never cast
+        down: scored in fp64 with the bits of `Index.dense_search_f64`) or term_lists (one int32 sequence per query; an
+        empty one = no BM25 for that query).  Legs of the three kinds may be mixed.
     `expect` (int64 per query): also return the 1-based rank of that document in each answer (-1: absent);
     `want_ids=False` then skips the id lists altogether.
     -> (ids [nq, top_n] int64 (-1 padded) or None, scores [nq, top_n] float64 or None, counts [nq] int32)
@@ -159,7 +171,7 @@ def rank_batch_group(legs: Sequence[dict], n_queries: int, similarity_k: int, wr
     """`anrag_shard_group_rank_batch`: `rank_batch` for legs that live on shard groups -- a leg's `index` is a
     `ShardGroup` or an `Index`, the legs may sit on different groups, shard counts and devices.  Same arguments, same
     return shapes, and the same ids, counts, ranks and score bits as `rank_batch` on ONE index holding the whole corpus
-    (`doc_of_row` maps the leg's GLOBAL rows)."""
+    (`doc_of_row` maps the leg's GLOBAL rows).  A `queries_f64` leg is not served on shard groups: `AnragError(-1)`."""
     lib = nat.load_library()
     arr = (nat.GroupRankLeg * len(legs))()
     keep = []
@@ -532,6 +544,13 @@ class Index:
         """(float64 queries answered by the list scan, by the score array + sort) since the index was created."""
         a, b = C.c_int64(0), C.c_int64(0)
         nat.check(self._lib.anrag_dense_f64_stats(self.handle, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def rank_f64_tile_stats(self) -> tuple:
+        """(float64 list queries of `queries_f64` legs scored by the fp64 tile kernel, by per-query score passes) since
+        the index was created (`anrag_rank_f64_tile_stats`)."""
+        a, b = C.c_int64(0), C.c_int64(0)
+        nat.check(self._lib.anrag_rank_f64_tile_stats(self.handle, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def set_dense_f64_prefilter(self, on: bool = True) -> None:

@@ -268,6 +268,8 @@ class RetrievalEvaluationSystem:
 
         if self._on_shard_group(self.embeddings_data.get(source_enum, {}), bm25):
             return None
+        if any(isinstance(query_embeddings.get(key), np.ndarray) and query_embeddings[key].dtype != np.float32 for key, _ in active):
+            return None  # (float64 LISTS take `_rank_batch`'s fp64 tiles; one float64 query keeps the per-leg route)
         if want_bm25 and not (query_tokens or query_text):
             logger.warning("BM25 search requested but no query_text or query_tokens provided - skipping BM25")
         params = dict(similarity_k=similarity_k, common_sections_n=common_sections_n, info_source=source_enum.value,
@@ -348,6 +350,7 @@ class RetrievalEvaluationSystem:
         # (which models can take part is a property of the call, not of a query: `DataFrame.empty` alone costs a microsecond,
         # and this loop runs thousands of times per evaluation call)
         usable = [key for key, _, _ in self.config.DENSE_MODELS if key in dims and model_weights.get(key, 0) > 0]
+        leg_dtype = {}
         for q in queries:
             qe = q["query_embeddings"]
             keys = [key for key in usable if key in qe]
@@ -356,16 +359,26 @@ class RetrievalEvaluationSystem:
             active = keys
             for key in keys:
                 e = q["query_embeddings"][key]
-                if e.dtype != np.float32 or e.size != dims[key]:
-                    return None  # fp64 queries are scored in fp64 by the per-query path (search_engine.py:157)
+                if e.dtype not in (np.float32, np.float64) or e.size != dims[key]:
+                    return None
+                # float64 embeddings (search_engine.py:157) are scored in fp64: a `queries_f64` leg, the bits of the
+                # per-query path; a model's embeddings must be of one dtype across the list
+                if leg_dtype.setdefault(key, e.dtype) != e.dtype:
+                    return None
+        if any(dt == np.float64 for dt in leg_dtype.values()):
+            if on_group:
+                return None  # float64 legs are not served on shard groups: one by one
+            if len(queries) < self.RANKED_LIST_MIN and similarity_k <= 64:
+                return None  # short small-k float64 lists: the per-query fp64 routes (K1D / K1FD)
         se = self.search_engine
         legs = []
         for key in active:
             df = embeddings_dict[key]
             h = DenseHandle.of(df)
             allow = _allow_of(h, "dense", flt) if flt else None
+            emb = np.stack([q["query_embeddings"][key].reshape(-1) for q in queries])
             legs.append(dict(index=h.index, weight=model_weights.get(key, 1.0), allow=allow,
-                             queries=np.stack([q["query_embeddings"][key].reshape(-1) for q in queries]),
+                             **({"queries_f64": emb} if leg_dtype[key] == np.float64 else {"queries": emb}),
                              doc_of_row=self._gids(source_enum, ("dense", id(df)), df["id"].tolist())))
         if want_bm25:
             from .preprocess_bm25 import preprocess_text
@@ -411,8 +424,9 @@ class RetrievalEvaluationSystem:
         route's envelope (one dense model + BM25, ids out, no rerank, similarity_k <= 64) in lists of fewer than 16 go to
         the library as ONE `anrag_hybrid_search_batch` (the device pipeline, a single host sync); other ids-only requests
         -- longer lists, any number of dense models, with or without BM25, similarity_k up to retrieval_eval's 12,000 --
-        as ONE `anrag_rank_batch`;
-        anything else (reranking, `return_docs`, float64 embeddings) is answered by the per-query method."""
+        as ONE `anrag_rank_batch`.  Float64 embeddings (scored in fp64, the per-query method's bits) take that route as
+        fp64 score tiles from 16 queries on and at similarity_k > 64; shorter small-k float64 lists, float64 lists on a
+        shard group, and anything else (reranking, `return_docs`) are answered by the per-query method."""
         def one_by_one():
             return [self.retrieve_documents(**q, **params) for q in queries]
 
@@ -488,7 +502,7 @@ class RetrievalEvaluationSystem:
             if not tokens:
                 return ranked()
             if np.asarray(q["query_embeddings"][keys]).dtype == np.float64:
-                return one_by_one()  # scored in fp64 by the per-query route
+                return one_by_one()  # a short small-k float64 list: scored in fp64 by the per-query route
             token_lists.append(tokens)
         try:
             emb = np.stack([np.asarray(q["query_embeddings"][keys], dtype=np.float32).reshape(-1) for q in queries])

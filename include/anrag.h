@@ -419,6 +419,12 @@ int anrag_hybrid_search_batch(anrag_index *idx, const float *queries, const int3
  * first, BM25 last):
  *   kind ANRAG_LEG_DENSE  idx's dense rows, ranked by fp32 dot product with queries[q] (host, [n_queries][dim]) --
  *                         the arithmetic of anrag_dense_search, bit for bit
+ *   kind ANRAG_LEG_DENSE_F64  idx's dense rows, ranked by the fp64 dot product with float64 queries: `queries` then points
+ *                         at double [n_queries][dim] on the host (cast the pointer: (const float *)my_doubles; the
+ *                         struct's layout is the same for every kind).  The arithmetic of anrag_dense_search_f64, bit
+ *                         for bit: fp64 score tiles (K1TD) at the dimensions that have a tile kernel, one fp64 score pass
+ *                         per query at the others.  A row whose score is -inf is not a candidate, as there.  Lists order
+ *                         (score desc, row asc) with -0.0 == +0.0
  *   kind ANRAG_LEG_BM25   idx's BM25 rows, ranked by BM25 score of query q's term ids
  *                         term_ids[term_offsets[q] .. term_offsets[q+1]) (host); a query WITHOUT term ids has no such
  *                         leg, as the reference skips BM25 for it (src/search_engine.py:216-217)
@@ -436,15 +442,17 @@ int anrag_hybrid_search_batch(anrag_index *idx, const float *queries, const int3
  * expect_id / out_rank (nullable, together) [n_queries]: out_rank[q] = 1-based position of document expect_id[q] in
  * query q's answer, -1 if it is not there -- what retrieval_eval.py:75-82 looks for in the returned list; with
  * out_id == NULL only counts and ranks come back (an evaluation run over thousands of queries needs nothing else).
- * Envelope: min(similarity_k, rows) <= 16384 for a dense leg, <= 13312 for a BM25 leg, min(top_n, entries) <= 13312
+ * Legs of the three kinds may be mixed in one call.
+ * Envelope: min(similarity_k, rows) <= 16384 for a dense leg, <= 13312 for a float64 dense leg or a BM25 leg, min(top_n, entries) <= 13312
  * when fusing (anrag_rank_caps); all legs on one device.  Outside it: ANRAG_ERR_INVALID -- use the per-query entry
  * points (any k). */
 #define ANRAG_LEG_DENSE 0
 #define ANRAG_LEG_BM25 1
+#define ANRAG_LEG_DENSE_F64 2
 typedef struct anrag_rank_leg {
     anrag_index *idx;
     int32_t kind;
-    const float *queries;
+    const float *queries; /* ANRAG_LEG_DENSE_F64: const double [n_queries][dim], cast */
     const int32_t *term_ids;
     const int64_t *term_offsets;
     const uint8_t *allow_source;
@@ -455,7 +463,10 @@ typedef struct anrag_rank_leg {
 int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int32_t n_queries, int32_t similarity_k,
                      double wrrf_k, int32_t top_n, int64_t id_space, int64_t *out_id, double *out_score,
                      int32_t *out_count, const int64_t *expect_id, int32_t *out_rank);
-/* Largest list a dense (fp32 scores) / BM25 or fused (fp64 scores) ranking of anrag_rank_batch can return. */
+/* Cumulative for this index: float64 queries of ANRAG_LEG_DENSE_F64 legs scored by the fp64 tile kernel (K1TD) and by
+ * per-query score passes (a dimension without a tile kernel, or ANRAG_RANK_SCAN_TILES set in the environment). */
+int anrag_rank_f64_tile_stats(anrag_index *idx, int64_t *tiled, int64_t *passed);
+/* Largest list a dense (fp32 scores) / float64 dense, BM25 or fused (fp64 scores) ranking of anrag_rank_batch can return. */
 int anrag_rank_caps(int32_t *out_k_max_fp32, int32_t *out_k_max_fp64);
 /* The select behind a ranking has two forms for a segment (one query's scores of one leg, or its fused sums) longer
  * than the list cap: narrow = one workgroup per segment, right for lists of queries; wide = a segment cut into slices
@@ -701,7 +712,8 @@ int anrag_shard_group_debug_enqueue(anrag_shard_group *g, int64_t *out_groups, i
  * a model that is not sharded); exactly one of the two is set.  The legs of a call may sit on different groups, with
  * different shard counts, and on different devices.  doc_of_row is the map of the leg's GLOBAL rows.  The envelope is
  * anrag_rank_caps applied to the global lists: min(similarity_k, global rows) <= 16384 for a dense leg, <= 13312 for a
- * BM25 leg, the fused cut <= 13312; outside it ANRAG_ERR_INVALID.
+ * BM25 leg, the fused cut <= 13312; outside it ANRAG_ERR_INVALID.  Float64 legs (ANRAG_LEG_DENSE_F64) are not served
+ * on shard groups: that kind is ANRAG_ERR_INVALID here, like any kind other than the two below.
  * Per chunk of queries and leg, shard s runs the score tiles and the per-query sort (k_s = min(similarity_k, its rows))
  * on its own primary stream out of its own grow-only scratch and records an event; the home device (leg 0's shard 0)
  * waits for the events on its stream, merges the S sorted lists of every query with ONE kernel per leg -- score desc,
