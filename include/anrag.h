@@ -318,7 +318,11 @@ int anrag_bm25_scores(anrag_index *idx, const int32_t *term_ids, int32_t n_terms
  * by the caller's truncation to common_sections_n (query_rag_retrieval.py:360-362):
  *   score[id] += weight[l] * (1 / (k + rank)), rank from 1, lists in order;
  *   stable sort by score descending (ties keep first-insertion order).
- * ids: host, the lists concatenated; list_len[l] entries each. fp64, bit-exact. */
+ * ids: host, the lists concatenated; list_len[l] entries each. fp64, bit-exact.
+ * A negative id is padding, in every form of the kernel (one workgroup, all-pairs
+ * grid, radix sorts): it occupies its rank -- the entries behind it keep theirs --
+ * contributes nothing and is never returned.  1 <= n_lists <= ANRAG_WRRF_MAX_LISTS,
+ * empty lists allowed. */
 int anrag_wrrf(anrag_index *idx, const int64_t *ids, const int32_t *list_len,
                const double *weight, int32_t n_lists, double k, int32_t top_n, int64_t *out_id,
                double *out_score, int32_t *out_count);
@@ -502,6 +506,15 @@ int anrag_debug_rank_select(anrag_index *idx, const void *keys, int32_t fp64, co
  * k records each into the global top-k (score desc, doc asc -- row order is
  * shard-local, doc ids are global and ascend with rows under row sharding).
  * List l starts at d_lists + l * list_stride records (list_stride >= k).
+ * PRECONDITION: inside a list the records are in (score desc, doc asc) order,
+ * equal scores included, padding (doc < 0) only at its tail, no NaN score (the
+ * scans report a NaN dot product as +inf; +inf and ties among +inf are fine).  A
+ * list is read only up to its first record that does not enter the running top
+ * k, so a record behind an out-of-order one is never seen:
+ * [(1.0,5),(1.0,6)] + [(1.0,8),(1.0,3)], k = 2 gives docs (5,6), not (3,5).  The
+ * candidate entry points produce such lists whenever doc ids ascend with rows
+ * (doc_id_base, or an ascending doc_id array); for other doc ids use a shard
+ * group, which merges in shard order.  The order of the lists does not matter.
  * All device pointers; enqueued on the fusion stream. */
 int anrag_merge_candidates_device(anrag_index *idx, const anrag_candidate *d_lists,
                                   int32_t n_lists, int32_t k, int64_t list_stride,
@@ -537,13 +550,20 @@ int anrag_hybrid_candidates_group_device(anrag_index *idx, const float *const *d
  * top-k, then weighted RRF on those global ranks + top-n
  * -> d_out + q*top_n, d_count[q].  Exchanging several in-flight queries per
  * all-gather amortises the collective's fixed cost (each query is still
- * scanned on its own: batch = 1 kernels). */
+ * scanned on its own: batch = 1 kernels).  PRECONDITION on every list of k
+ * records: that of anrag_merge_candidates_device.  list_stride >= 2k *
+ * n_queries; records outside the n_queries blocks of a slab are not read.  A
+ * padding record of a merged list keeps its rank and adds nothing; d_out + q *
+ * top_n is written up to d_count[q] = min(top_n, distinct docs) only. */
 int anrag_merge_fuse_device(anrag_index *idx, const anrag_candidate *d_lists, int32_t n_lists,
                             int32_t k, int64_t list_stride, double w_dense, double w_bm25,
                             double wrrf_k, int32_t top_n, int32_t n_queries,
                             anrag_candidate *d_out, int32_t *d_count);
 /* WRRF over two device candidate lists (dense, bm25) -> top_n on the device
- * (fusion stream). */
+ * (fusion stream).  Only the doc ids are read: a record with doc < 0 is padding
+ * wherever it stands (it occupies its rank and is never returned), and the lists
+ * need not be sorted.  0 < n_dense + n_bm25 <= 1024; d_out is written up to
+ * *d_count = min(top_n, distinct docs) only. */
 int anrag_wrrf_device(anrag_index *idx, const anrag_candidate *d_dense, int32_t n_dense,
                       const anrag_candidate *d_bm25, int32_t n_bm25, double w_dense,
                       double w_bm25, double k, int32_t top_n, anrag_candidate *d_out,

@@ -55,6 +55,108 @@ def test_wrrf_long_lists(idx):
             assert out_score.tolist() == [s for _, s in want]
 
 
+# ---- anrag_wrrf at its form switches: one workgroup (M <= 1024), the all-pairs grid with 1024-entry tiles (<= 4096), three
+# radix sorts above.  Inputs: tests/shard_merge_model.py, held to what they claim by tests/test_shard_merge_model_cpu.py.
+SWITCH_M = (1, 63, 64, 65, 1023, 1024, 1025, 4095, 4096, 4097)
+W3 = {"a": 5.0, "b": 1.0, "c": 2.0}
+
+
+def _assert_wrrf(idx, lists, weights, k, top_n, ref, what):
+    out_id, out_score = idx.wrrf(lists, weights, k, top_n)
+    want = ref[:top_n]
+    assert out_id.tolist() == [i for i, _ in want], what
+    assert out_score.view(np.int64).tolist() == np.array([s for _, s in want], np.float64).view(np.int64).tolist(), what
+    return out_id, out_score
+
+
+@pytest.mark.parametrize("m_total", SWITCH_M)
+def test_wrrf_at_the_form_switches(idx, m_total):
+    """M on both sides of every switch and tile edge, over 3 lists that share a third of their ids; top_n in
+    {1, distinct, distinct + 5}; then with a negative weight, where fused scores go below zero (the sorted form's -inf
+    filler slots must still sort behind them)."""
+    import shard_merge_model as model
+    from oracle import ref_search
+
+    lists = model.wrrf_switch_lists(m_total)
+    for weights in (W3, {"a": 5.0, "b": -1.0, "c": 2.0}, {"a": -5.0, "b": -1.0, "c": -2.0}):
+        ref = ref_search.weighted_reciprocal_rank_fusion(list(zip(lists, "abc")), weights, 40)
+        assert weights is W3 or m_total < 63 or min(s for _, s in ref) < 0
+        for top_n in (1, len(ref), len(ref) + 5):
+            _assert_wrrf(idx, lists, [weights[n] for n in "abc"], 40, top_n, ref, (m_total, weights["b"], top_n))
+
+
+@pytest.mark.parametrize("m_total", [4096, 4097])
+def test_wrrf_one_id_in_four_tiles(idx, m_total):
+    """One id at entries 5, 1030, 2100 and 4090: owner and duplicates in different 1024-entry tiles of the grid form
+    (M = 4096), in one group of the sorted form (M = 4097); twice inside the first list."""
+    import shard_merge_model as model
+    from oracle import ref_search
+
+    lists = model.wrrf_switch_lists(m_total, seed=1)
+    lens = [len(l) for l in lists]
+    flat = np.concatenate(lists)
+    flat[[5, 1030, 2100, 4090]] = 10 ** 7
+    lists = [l.tolist() for l in np.split(flat, np.cumsum(lens)[:-1])]
+    assert lists[0].count(10 ** 7) == 2 and lists[1].count(10 ** 7) == 1 and lists[2].count(10 ** 7) == 1
+    ref = ref_search.weighted_reciprocal_rank_fusion(list(zip(lists, "abc")), W3, 40)
+    assert 10 ** 7 in [i for i, _ in ref[:30]]
+    for top_n in (1, 30, len(ref)):
+        _assert_wrrf(idx, lists, [W3[n] for n in "abc"], 40, top_n, ref, (m_total, top_n))
+
+
+@pytest.mark.parametrize("scale", [1, 4, 8])
+def test_wrrf_sixteen_lists_some_empty(idx, scale):
+    """ANRAG_WRRF_MAX_LISTS lists with empty ones first, in the middle and last, in all three forms (M = 773, 3092, 6184);
+    17 lists are refused."""
+    from anrag import _native as nat
+    from oracle import ref_search
+
+    lens = [scale * n for n in (0, 0, 70, 0, 5, 300, 0, 0, 1, 64, 0, 200, 33, 90, 10, 0)]
+    rng = np.random.default_rng(scale)
+    lists = [rng.permutation(2 * max(lens))[:n].tolist() for n in lens]
+    names = [f"l{i}" for i in range(16)]
+    weights = {n: float(w) for n, w in zip(names, rng.integers(0, 6, size=16))}
+    ref = ref_search.weighted_reciprocal_rank_fusion(list(zip(lists, names)), weights, 60)
+    for top_n in (1, 15, len(ref)):
+        _assert_wrrf(idx, lists, [weights[n] for n in names], 60, top_n, ref, (scale, top_n))
+    with pytest.raises(nat.AnragError):
+        idx.wrrf(lists + [[1, 2, 3]], [weights[n] for n in names] + [1.0], 60, 10)
+
+
+@pytest.mark.parametrize("m_total", [1000, 3000, 6000])
+def test_wrrf_wide_ids(idx, m_total):
+    """Ids 2^40 + i, and the largest id there is, 2^63 - 1, in two of the lists."""
+    import shard_merge_model as model
+    from oracle import ref_search
+
+    lists = model.wrrf_switch_lists(m_total, seed=2, base=2 ** 40)
+    top = 2 ** 63 - 1
+    lists[0][len(lists[0]) // 2] = top
+    lists[2][-1] = top
+    ref = ref_search.weighted_reciprocal_rank_fusion(list(zip(lists, "abc")), W3, 40)
+    assert min(i for i, _ in ref) >= 2 ** 40 and top in dict(ref)
+    for top_n in (10, len(ref)):
+        _assert_wrrf(idx, lists, [W3[n] for n in "abc"], 40, top_n, ref, (m_total, top_n))
+
+
+def test_wrrf_negative_ids_are_padding_in_every_form(idx):
+    """A negative id occupies its rank, contributes nothing and is never returned: the same 3 x 300 entries, filled up with
+    neutral ids to M = 1000 (one workgroup), 3000 (grid) and 6000 (sorted), equal `wrrf_padded`, and the three answers agree
+    on the ids of the shared content."""
+    import shard_merge_model as model
+
+    content = []
+    for m_total in (1000, 3000, 6000):
+        lists = model.wrrf_negative_lists(m_total)
+        ref = model.wrrf_padded(lists, [5.0, 1.0, 2.0], 40)
+        for top_n in (10, len(ref), m_total):
+            out_id, out_score = _assert_wrrf(idx, lists, [5.0, 1.0, 2.0], 40, top_n, ref, (m_total, top_n))
+            assert len(out_id) == min(top_n, len(ref)) and (out_id >= 0).all()
+        keep = out_id < 10 ** 6
+        content.append((out_id[keep].tolist(), out_score[keep].view(np.int64).tolist()))
+    assert len(content[0][0]) > 300 and content[0] == content[1] == content[2]
+
+
 def test_hybrid_matches_oracle(idx):
     from oracle import ref_search
     from oracle.make_golden import synth_chunks, synth_dense, synth_query

@@ -76,22 +76,14 @@ class OracleShardEngine:
         self._write(out[k:], top + self.lo, sc[top], k)
 
     def merge_fuse(self, lists, n_lists, k, stride, w_dense, w_bm25, wrrf_k, top_n, n_queries, out, count):
-        rec = lists.numpy().reshape(-1, 2)
-        for q in range(n_queries):
-            merged = []
-            for leg in range(2):
-                cands = []
-                for l in range(n_lists):
-                    base = l * stride + q * 2 * k + leg * k
-                    for r in rec[base: base + k]:
-                        if r[1] >= 0:
-                            cands.append((float(np.int64(r[0]).view(np.float64)), int(r[1])))
-                cands.sort(key=lambda c: (-c[0], c[1]))
-                merged.append([c[1] for c in cands[:k]])
-            fused = ref_search.weighted_reciprocal_rank_fusion(
-                [(merged[0], "d"), (merged[1], "b")], {"d": w_dense, "b": w_bm25}, int(wrrf_k))[:top_n]
-            self._write(out[q], [i for i, _ in fused], [s for _, s in fused], top_n)
-            count[q] = len(fused)
+        # the one statement of the operation: tests/shard_merge_model.py, which the HIP kernel is tested against too
+        # (tests/test_gpu_shard_merge.py)
+        import shard_merge_model
+
+        ids, sbits, counts = shard_merge_model.merge_fuse(lists.numpy(), n_lists, k, stride, w_dense, w_bm25, wrrf_k,
+                                                          top_n, n_queries)
+        out[:n_queries].copy_(torch.from_numpy(np.stack([sbits, ids], axis=2)))
+        count[:n_queries] = torch.from_numpy(counts)
 
 
 class GroupedOracleShardEngine(OracleShardEngine):
