@@ -489,7 +489,9 @@ int enqueue_candidates_2k(anrag_index *idx, const CandQuery *q, int32_t n, int32
                           const uint32_t *d_allow_bm25);
 int reserve_call_pool(anrag_index *idx, int64_t bytes, char **out);
 
-// ---- full ranking (rank_batch.hip): the pieces anrag_rank_batch and anrag_shard_group_rank_batch share
+// ---- full ranking (rank_batch.hip): the pieces anrag_rank_batch and anrag_shard_group_rank_batch share: the call plan
+// (RankPlan: checks, fusion plan, chunk), a leg's share on one index and its producer (RankLegRun, rank_leg_chunk), the
+// per-call uploads (rank_stage_*), and everything behind the legs' lists (RankTail)
 int rank_list_cap(bool fp64);  // anrag_rank_caps
 // The wide form of the select (rank_batch.hip, "K4 wide") needs scratch of the caller's rank_pool: rank_wide_bytes for
 // the launch's segments, asked for where rank_wide_wanted says the current mode would take it.
@@ -507,8 +509,74 @@ int64_t rank_wide_bytes(bool fp64, int32_t n_seg);
 int launch_rank_sort(int device, hipStream_t st, int32_t n_seg, const void *keys, bool fp64, int64_t key_stride, int32_t n,
                      int32_t k, const int32_t *seg_k, uint32_t *out_rows, double *out_keys, int64_t out_stride,
                      int32_t *out_count, const RankWide &wide = RankWide());
-// every map inside [0, id_space) and injective (a NULL map: the leg's rows fit the id space)
-int rank_check_maps(int32_t n_legs, const int64_t *const *maps, const int64_t *leg_rows, int64_t id_space);
+// a leg's host operands, whichever entry point's leg struct they came in
+struct RankLegOps {
+    int32_t kind = 0;
+    const void *queries = nullptr;  // float, or double for ANRAG_LEG_DENSE_F64: [n_queries][dim]
+    const int32_t *term_ids = nullptr;
+    const int64_t *term_offsets = nullptr;
+    const uint8_t *allow_source = nullptr;
+    int32_t n_sources = 0;
+    const int64_t *doc_of_row = nullptr;
+    double weight = 0;
+};
+template <class Leg>
+inline RankLegOps rank_leg_ops(const Leg &g) {
+    return RankLegOps{g.kind, g.queries, g.term_ids, g.term_offsets, g.allow_source, g.n_sources, g.doc_of_row, g.weight};
+}
+// The plan of a call, in the order the steps run: rank_plan_call, rank_plan_kind per leg (before any lock),
+// rank_plan_leg per leg on its GLOBAL rows, rank_plan_fusion; the caller adds what its legs take per query of a chunk
+// (`per_query`) and per call (`fixed`); rank_plan_chunk.
+struct RankPlan {
+    int32_t n_legs = 0, n_queries = 0, similarity_k = 0, top_n = 0;
+    double wrrf_k = 0;
+    int64_t id_space = 0;
+    int64_t leg_rows[ANRAG_WRRF_MAX_LISTS] = {};
+    int32_t leg_k[ANRAG_WRRF_MAX_LISTS] = {};  // min(similarity_k, rows)
+    bool fuse = false, fuse_in_lds = false;    // in LDS: rank_fuse_sort_kernel does the whole fusion
+    int32_t fuse_n = 0, out_n = 0;             // entries the fused order is cut to; entries a query returns
+    int64_t per_query = 0, fixed = 0;          // bytes of scratch
+    int64_t chunk = 0, max_terms_chunk = 0;    // queries per chunk; the most term ids a chunk of a BM25 leg carries
+    int32_t c_full = 0;                        // segments of a full chunk's sort launches
+};
+int rank_plan_call(RankPlan &p, bool have_legs, int32_t n_legs, int32_t n_queries, int32_t similarity_k, double wrrf_k,
+                   int32_t top_n, int64_t id_space, const int64_t *out_id, const double *out_score, const int32_t *out_count,
+                   const int64_t *expect_id, const int32_t *out_rank);
+int rank_plan_kind(int l, const RankLegOps &g, unsigned kinds);  // `kinds`: bit (1 << kind) per kind the route admits
+int rank_plan_index(int l, const RankLegOps &g, const anrag_index *ix);  // a leg on ONE index: loaded, source ids there
+int rank_plan_leg(RankPlan &p, int l, const RankLegOps &g, int64_t rows);
+// fuse_n, fuse_in_lds, out_n; every map inside [0, id_space) and injective (a NULL map: the leg's rows fit the id space)
+int rank_plan_fusion(RankPlan &p, const RankLegOps *legs);
+void rank_plan_chunk(RankPlan &p, const RankLegOps *legs);  // 6 GiB of scratch a chunk, or ANRAG_RANK_CHUNK_BUDGET
+// One leg's share on one index: all of it (anrag_rank_batch) or a shard's block of rows.  The buffers are device memory
+// of ix's device, the staging vectors stay as they are until the chunk's host sync.
+struct RankLegRun {
+    anrag_index *ix = nullptr;
+    hipStream_t st = nullptr;  // every copy and launch of the run
+    int32_t kind = 0;
+    int64_t rows = 0, stride = 0;
+    int32_t k = 0;  // min(similarity_k, rows)
+    uint32_t *allow = nullptr;
+    void *q = nullptr;  // float, or double for ANRAG_LEG_DENSE_F64
+    int32_t *terms = nullptr, *seg_k = nullptr;
+    int64_t *term_off = nullptr;
+    void *scores = nullptr;
+    uint32_t *list_rows = nullptr;
+    double *list_keys = nullptr;  // nullable
+    int32_t *list_cnt = nullptr;
+    RankWide wide;  // the wide select's scratch, where the mode takes it for these rows
+    std::vector<int32_t> h_segk;
+    std::vector<int64_t> h_off;
+    void carve(Carver &cv, const RankPlan &p, bool want_allow, bool want_keys);
+};
+struct RankTail;
+// One chunk (queries q0 .. q0 + c) of a leg on run.ix, whose device is current: operands up, score tiles (K1T / K1TD, a
+// pass per query where the dimension has no tile kernel; K3's score table), then the sort into the run's lists -- or,
+// with `count`, the rank of count->d_expect in leg 0's order alone (rank_count_kernel; no lists).  Never syncs.
+int rank_leg_chunk(RankLegRun &run, const RankLegOps &g, int64_t q0, int32_t c, const RankTail *count);
+// per-call uploads on the run's / the given stream, each followed by its host sync
+int rank_stage_allow(const RankLegRun &run, const RankLegOps &g);  // no-op without an allow list
+int rank_stage_map(hipStream_t st, const int64_t *doc_of_row, int64_t rows, int32_t *d_map);  // int64 -> int32
 struct RankTailLeg {
     const uint32_t *rows;       // [chunk][leg_k]
     const double *row_keys;     // one leg only
@@ -530,15 +598,17 @@ struct RankTail {
     double *d_f = nullptr, *d_skey = nullptr;  // fusion in HBM
     uint32_t *d_t = nullptr, *d_stie = nullptr;
     int32_t *d_scnt = nullptr;
-    uint64_t *d_fuse_legs = nullptr;           // fusion in LDS: rank_fuse_table's words
+    uint64_t *d_fuse_legs = nullptr;           // fusion in LDS: rank_stage_fuse_table's words
     int64_t *d_out_id = nullptr;
     double *d_out_score = nullptr;
     int32_t *d_out_cnt = nullptr;
     int64_t *d_expect = nullptr;
     int32_t *d_rank = nullptr;
     RankWide wide;                             // for the fused-sums select (fusion in HBM)
+    void carve(Carver &cv, const RankPlan &p, bool want_expect);  // the plan's figures and every buffer above; not leg[]
 };
-void rank_fuse_table(const RankTail &t, uint64_t *tab);  // 6 * ANRAG_WRRF_MAX_LISTS words
+int rank_stage_fuse_table(const RankTail &t);  // fusion in LDS: the table of the filled leg[] up, and its host sync
+int rank_stage_expect(const RankTail &t, const int64_t *expect_id, int64_t q0, int32_t c);  // a chunk's; no sync
 int launch_rank_tail(const RankTail &t, int32_t c, bool want_ids);
 int rank_copy_out(const RankTail &t, int32_t c, int64_t q0, int32_t top_n, int64_t *out_id, double *out_score,
                   int32_t *out_count, int32_t *out_rank);

@@ -1297,20 +1297,79 @@ int launch_rank_sort(int device, hipStream_t st, int32_t n_seg, const void *keys
                                          out_rows, out_keys, out_stride, out_count, wide);
 }
 
-int rank_check_maps(int32_t n_legs, const int64_t *const *maps, const int64_t *leg_rows, int64_t id_space) {
+int rank_plan_call(RankPlan &p, bool have_legs, int32_t n_legs, int32_t n_queries, int32_t similarity_k, double wrrf_k,
+                   int32_t top_n, int64_t id_space, const int64_t *out_id, const double *out_score, const int32_t *out_count,
+                   const int64_t *expect_id, const int32_t *out_rank) {
+    ANRAG_REQUIRE(have_legs && n_legs >= 1 && n_legs <= ANRAG_WRRF_MAX_LISTS, "n_legs %d out of range [1, %d]", n_legs,
+                  ANRAG_WRRF_MAX_LISTS);
+    ANRAG_REQUIRE(n_queries >= 0 && n_queries <= (1 << 22), "n_queries %d out of range", n_queries);
+    ANRAG_REQUIRE(similarity_k > 0 && top_n > 0, "similarity_k and top_n must be positive");
+    ANRAG_REQUIRE(out_count != nullptr, "out_count is NULL");
+    ANRAG_REQUIRE(!out_score || out_id, "out_score without out_id");
+    ANRAG_REQUIRE((expect_id != nullptr) == (out_rank != nullptr), "expect_id and out_rank come together");
+    ANRAG_REQUIRE(out_id || out_rank, "nothing to return: out_id and out_rank are both NULL");
+    p.n_legs = n_legs;
+    p.n_queries = n_queries;
+    p.similarity_k = similarity_k;
+    p.top_n = top_n;
+    p.wrrf_k = wrrf_k;
+    p.id_space = id_space;
+    p.fuse = n_legs > 1;
+    return ANRAG_OK;
+}
+
+int rank_plan_kind(int l, const RankLegOps &g, unsigned kinds) {
+    ANRAG_REQUIRE(g.kind >= 0 && g.kind < 32 && ((kinds >> g.kind) & 1u), "leg %d: kind %d", l, g.kind);
+    ANRAG_REQUIRE(g.weight > 0.0 && g.weight < __builtin_huge_val(), "leg %d: weight must be positive and finite", l);
+    return ANRAG_OK;
+}
+
+int rank_plan_index(int l, const RankLegOps &g, const anrag_index *ix) {
+    if (g.kind == ANRAG_LEG_BM25) {
+        ANRAG_REQUIRE(ix->d_post_doc != nullptr, "leg %d: BM25 ranking before anrag_bm25_load", l);
+        ANRAG_REQUIRE(!(g.allow_source && !ix->d_bm25_src), "leg %d: a source filter needs source ids", l);
+    } else {
+        ANRAG_REQUIRE(ix->d_emb != nullptr, "leg %d: dense ranking before anrag_dense_load", l);
+        ANRAG_REQUIRE(!(g.allow_source && !ix->d_dense_src), "leg %d: a source filter needs source ids", l);
+    }
+    return ANRAG_OK;
+}
+
+int rank_plan_leg(RankPlan &p, int l, const RankLegOps &g, int64_t rows) {
+    if (g.kind == ANRAG_LEG_BM25) {
+        ANRAG_REQUIRE(g.term_offsets != nullptr && g.term_offsets[0] == 0, "leg %d: bad term offsets", l);
+        ANRAG_REQUIRE(g.term_offsets[p.n_queries] == 0 || g.term_ids != nullptr, "leg %d: term_ids is NULL", l);
+        for (int32_t q = 0; q < p.n_queries; ++q)
+            ANRAG_REQUIRE(g.term_offsets[q + 1] >= g.term_offsets[q] && g.term_offsets[q + 1] - g.term_offsets[q] <= 4096,
+                          "leg %d, query %d: term count out of range [0, 4096]", l, q);
+    } else {
+        ANRAG_REQUIRE(g.queries != nullptr, "leg %d: queries is NULL", l);
+    }
+    ANRAG_REQUIRE(rows > 0 && rows < 0x7FFFFFFFll, "leg %d: %lld rows (the batched ranking takes < 2^31)", l, (long long)rows);
+    ANRAG_REQUIRE(!g.allow_source || (g.n_sources >= 0 && g.n_sources <= 65536), "leg %d: n_sources out of range", l);
+    p.leg_rows[l] = rows;
+    p.leg_k[l] = (int32_t)std::min<int64_t>(p.similarity_k, rows);
+    const int32_t cap = rank_list_cap(g.kind != ANRAG_LEG_DENSE);
+    ANRAG_REQUIRE(p.leg_k[l] <= cap, "leg %d: min(similarity_k, rows) = %d is outside the batched ranking's envelope (%d)", l,
+                  p.leg_k[l], cap);
+    return ANRAG_OK;
+}
+
+static int rank_check_maps(const RankPlan &p, const RankLegOps *legs) {
     // a leg must name a document once and inside the id space: the additions of a document then happen in leg
     // order whatever the thread schedule (rank_accumulate_kernel)
+    const int64_t id_space = p.id_space;
     std::vector<uint64_t> seen((size_t)((id_space + 63) / 64));
-    for (int l = 0; l < n_legs; ++l) {
-        const int64_t *map = maps[l];
+    for (int l = 0; l < p.n_legs; ++l) {
+        const int64_t *map = legs[l].doc_of_row;
         if (!map) {  // row r is document r: injective as it stands
-            ANRAG_REQUIRE(leg_rows[l] <= id_space, "leg %d: %lld rows, documents [0, %lld)", l, (long long)leg_rows[l],
+            ANRAG_REQUIRE(p.leg_rows[l] <= id_space, "leg %d: %lld rows, documents [0, %lld)", l, (long long)p.leg_rows[l],
                           (long long)id_space);
             continue;
         }
         std::fill(seen.begin(), seen.end(), 0ull);
-        for (int64_t r = 0; r < leg_rows[l]; ++r) {
-            const int64_t d = map ? map[r] : r;
+        for (int64_t r = 0; r < p.leg_rows[l]; ++r) {
+            const int64_t d = map[r];
             ANRAG_REQUIRE(d >= 0 && d < id_space, "leg %d: row %lld maps to document %lld outside [0, %lld)", l,
                           (long long)r, (long long)d, (long long)id_space);
             ANRAG_REQUIRE(!((seen[(size_t)(d >> 6)] >> (d & 63)) & 1ull),
@@ -1322,9 +1381,109 @@ int rank_check_maps(int32_t n_legs, const int64_t *const *maps, const int64_t *l
     return ANRAG_OK;
 }
 
-void rank_fuse_table(const RankTail &t, uint64_t *tab) {
+int rank_plan_fusion(RankPlan &p, const RankLegOps *legs) {
+    if (p.fuse) {
+        ANRAG_REQUIRE(p.id_space > 0 && p.id_space < 0x7FFFFFFFll, "id_space %lld out of range", (long long)p.id_space);
+        int64_t sum_k = 0;
+        for (int l = 0; l < p.n_legs; ++l) sum_k += p.leg_k[l];
+        p.fuse_n = (int32_t)std::min<int64_t>(std::min<int64_t>(p.top_n, sum_k), p.id_space);
+        ANRAG_REQUIRE(p.fuse_n <= rank_cap<3>(), "min(top_n, entries) = %d is outside the batched ranking's envelope (%d)",
+                      p.fuse_n, rank_cap<3>());
+        p.fuse_in_lds = p.id_space <= rank_cap<3>() && !getenv("ANRAG_RANK_FUSE_IN_HBM");
+        if (int rc = rank_check_maps(p, legs)) return rc;
+    }
+    p.out_n = p.fuse ? p.fuse_n : (int32_t)std::min<int64_t>(p.top_n, p.leg_k[0]);
+    // what RankTail::carve takes
+    if (p.fuse && !p.fuse_in_lds) p.per_query += p.id_space * 12 + 512 + (int64_t)p.fuse_n * 12 + 512 + 4;
+    if (p.fuse) p.per_query += 4 + 256;
+    p.fixed += 1024;
+    p.per_query += (int64_t)p.out_n * 16 + 4 + 512 + 16;
+    return ANRAG_OK;
+}
+
+void rank_plan_chunk(RankPlan &p, const RankLegOps *legs) {
+    int64_t budget = 6ll << 30;
+    if (const char *e = getenv("ANRAG_RANK_CHUNK_BUDGET"))  // measurements and tests: bytes of scratch a chunk may take
+        budget = std::max<int64_t>(1, atoll(e));
+    p.chunk = std::max<int64_t>(1, std::min<int64_t>(p.n_queries, (budget - p.fixed) / std::max<int64_t>(p.per_query, 1)));
+    if (p.chunk > 8) p.chunk = p.chunk / 8 * 8;
+    p.max_terms_chunk = 0;
+    for (int l = 0; l < p.n_legs; ++l)
+        if (legs[l].kind == ANRAG_LEG_BM25)
+            for (int64_t q0 = 0; q0 < p.n_queries; q0 += p.chunk) {
+                const int64_t q1 = std::min<int64_t>(p.n_queries, q0 + p.chunk);
+                p.max_terms_chunk = std::max(p.max_terms_chunk, legs[l].term_offsets[q1] - legs[l].term_offsets[q0]);
+            }
+    // the wide select's scratch is sized for a full chunk, so a shorter last chunk that asks for it finds it there only
+    // if the full ones did
+    p.c_full = (int32_t)std::min<int64_t>(p.chunk, p.n_queries);
+}
+
+void RankLegRun::carve(Carver &cv, const RankPlan &p, bool want_allow, bool want_keys) {
+    const bool f64 = kind != ANRAG_LEG_DENSE;
+    const int64_t chunk = p.chunk, esz = f64 ? 8 : 4;
+    allow = want_allow ? cv.take<uint32_t>(kAllowWords) : nullptr;
+    if (kind == ANRAG_LEG_BM25) {
+        terms = cv.take<int32_t>(std::max<int64_t>(p.max_terms_chunk, 1));
+        seg_k = cv.take<int32_t>(chunk);
+        term_off = cv.take<int64_t>(chunk + 1);
+    } else {
+        q = cv.take<char>(chunk * ix->dim * esz);
+    }
+    scores = cv.take<char>(chunk * stride * esz);
+    list_rows = cv.take<uint32_t>(chunk * k);
+    list_keys = want_keys ? cv.take<double>(chunk * k) : nullptr;
+    list_cnt = cv.take<int32_t>(chunk);
+    wide.bytes = rank_wide_wanted(f64, p.c_full, (int32_t)rows) ? rank_wide_bytes(f64, p.c_full) : 0;
+    wide.scratch = wide.bytes ? cv.take<char>(wide.bytes) : nullptr;
+}
+
+int rank_stage_allow(const RankLegRun &r, const RankLegOps &g) {
+    if (!g.allow_source) return ANRAG_OK;
+    uint32_t h_bits[kAllowWords];
+    if (int rc = pack_allow_bits(g.allow_source, g.n_sources, h_bits)) return rc;
+    ANRAG_HIP(hipMemcpyAsync(r.allow, h_bits, sizeof(h_bits), hipMemcpyHostToDevice, r.st));
+    ANRAG_HIP(hipStreamSynchronize(r.st));  // h_bits goes out of scope
+    return ANRAG_OK;
+}
+
+int rank_stage_map(hipStream_t st, const int64_t *doc_of_row, int64_t rows, int32_t *d_map) {
+    std::vector<int32_t> h_map((size_t)rows);
+    for (int64_t i = 0; i < rows; ++i) h_map[(size_t)i] = (int32_t)doc_of_row[i];
+    ANRAG_HIP(hipMemcpyAsync(d_map, h_map.data(), (size_t)rows * 4, hipMemcpyHostToDevice, st));
+    ANRAG_HIP(hipStreamSynchronize(st));
+    return ANRAG_OK;
+}
+
+void RankTail::carve(Carver &cv, const RankPlan &p, bool want_expect) {
+    const int64_t chunk = p.chunk;
+    const bool in_hbm = p.fuse && !p.fuse_in_lds;
+    n_legs = p.n_legs;
+    fuse_in_lds = p.fuse_in_lds;
+    wrrf_k = p.wrrf_k;
+    id_space = p.id_space;
+    fuse_n = p.fuse_n;
+    out_n = p.out_n;
+    d_f = in_hbm ? cv.take<double>(chunk * id_space) : nullptr;
+    d_t = in_hbm ? cv.take<uint32_t>(chunk * id_space) : nullptr;
+    d_stie = in_hbm ? cv.take<uint32_t>(chunk * fuse_n) : nullptr;
+    d_skey = in_hbm ? cv.take<double>(chunk * fuse_n) : nullptr;
+    d_scnt = p.fuse ? cv.take<int32_t>(chunk) : nullptr;
+    d_fuse_legs = fuse_in_lds ? cv.take<uint64_t>(6 * ANRAG_WRRF_MAX_LISTS) : nullptr;
+    d_out_id = cv.take<int64_t>(chunk * out_n);
+    d_out_score = cv.take<double>(chunk * out_n);
+    d_out_cnt = p.fuse ? d_scnt : cv.take<int32_t>(chunk);
+    d_expect = want_expect ? cv.take<int64_t>(chunk) : nullptr;
+    d_rank = want_expect ? cv.take<int32_t>(chunk) : nullptr;
+    wide.bytes = in_hbm && rank_wide_wanted(true, p.c_full, (int32_t)id_space) ? rank_wide_bytes(true, p.c_full) : 0;
+    wide.scratch = wide.bytes ? cv.take<char>(wide.bytes) : nullptr;
+}
+
+// the legs' lists, counts, maps, strides and weights, as rank_fuse_sort_kernel reads them: the same for every chunk
+int rank_stage_fuse_table(const RankTail &t) {
+    if (!t.fuse_in_lds) return ANRAG_OK;
     constexpr int M = ANRAG_WRRF_MAX_LISTS;
-    memset(tab, 0, 6 * M * sizeof(uint64_t));
+    uint64_t tab[6 * M] = {};
     for (int l = 0; l < t.n_legs; ++l) {
         tab[l] = reinterpret_cast<uint64_t>(t.leg[l].rows);
         tab[M + l] = reinterpret_cast<uint64_t>(t.leg[l].cnt);
@@ -1333,6 +1492,16 @@ void rank_fuse_table(const RankTail &t, uint64_t *tab) {
         memcpy(&tab[4 * M + l], &t.leg[l].weight, 8);
     }
     tab[5 * M] = (uint64_t)t.n_legs;
+    ANRAG_HIP(hipMemcpyAsync(t.d_fuse_legs, tab, sizeof(tab), hipMemcpyHostToDevice, t.st));
+    ANRAG_HIP(hipStreamSynchronize(t.st));
+    return ANRAG_OK;
+}
+
+int rank_stage_expect(const RankTail &t, const int64_t *expect_id, int64_t q0, int32_t c) {
+    if (!expect_id) return ANRAG_OK;
+    ANRAG_HIP(hipMemcpyAsync(t.d_expect, expect_id + q0, (size_t)c * 8, hipMemcpyHostToDevice, t.st));
+    ANRAG_HIP(hipMemsetAsync(t.d_rank, 0xFF, (size_t)c * 4, t.st));  // -1: not in the answer
+    return ANRAG_OK;
 }
 
 // Fusion and emit of one chunk of c queries, behind the legs' lists (rows, counts; one leg: its keys too).
@@ -1409,6 +1578,83 @@ int rank_copy_out(const RankTail &t, int32_t c, int64_t q0, int32_t top_n, int64
     return ANRAG_OK;
 }
 
+int rank_leg_chunk(RankLegRun &r, const RankLegOps &g, int64_t q0, int32_t c, const RankTail *count) {
+    anrag_index *ix = r.ix;
+    hipStream_t st = r.st;
+    const int64_t stride = r.stride;
+    int rc;
+    if (r.kind == ANRAG_LEG_DENSE) {
+        const float *q = static_cast<const float *>(r.q);
+        float *tile = static_cast<float *>(r.scores);
+        ANRAG_HIP(hipMemcpyAsync(r.q, static_cast<const float *>(g.queries) + q0 * ix->dim, (size_t)c * ix->dim * sizeof(float),
+                                 hipMemcpyHostToDevice, st));
+        const int tile_n = getenv("ANRAG_RANK_SCAN_TILES") ? 0 : dense_tile_group_max(ix);
+        for (int32_t g0 = 0; tile_n > 0 && g0 < c; g0 += kTileLaunchMax)  // K1T: the rows once per launch
+            if ((rc = launch_dense_tile(ix, st, q + (int64_t)g0 * ix->dim, ix->dim, std::min<int32_t>(kTileLaunchMax, c - g0),
+                                        r.allow, tile + (int64_t)g0 * stride, stride)))
+                return rc;
+        for (int32_t g0 = tile_n > 0 ? c : 0; g0 < c; g0 += kScanGroupMax) {  // other dimensions: a pass per query
+            const int n = std::min<int32_t>(kScanGroupMax, c - g0);
+            const float *qs[kScanGroupMax];
+            int sets[kScanGroupMax];
+            for (int i = 0; i < n; ++i) {
+                qs[i] = q + (int64_t)(g0 + i) * ix->dim;
+                sets[i] = 0;  // unused: scores are written, no lists
+            }
+            if ((rc = launch_dense_scan_group(ix, st, qs, n, 0, r.allow, tile + (int64_t)g0 * stride, sets, stride))) return rc;
+        }
+    } else if (r.kind == ANRAG_LEG_DENSE_F64) {
+        // float64 queries: fp64 score tiles (K1TD, dense_tile_f64.hip), then the BM25 leg's path for an fp64 tile
+        const double *q = static_cast<const double *>(r.q);
+        double *tile = static_cast<double *>(r.scores);
+        ANRAG_HIP(hipMemcpyAsync(r.q, static_cast<const double *>(g.queries) + q0 * ix->dim,
+                                 (size_t)c * ix->dim * sizeof(double), hipMemcpyHostToDevice, st));
+        const int tile_n = getenv("ANRAG_RANK_SCAN_TILES") ? 0 : dense_tile_f64_group_max(ix);
+        for (int32_t g0 = 0; tile_n > 0 && g0 < c; g0 += kTileLaunchMax)  // the rows once per group of queries
+            if ((rc = launch_dense_tile_f64(ix, st, q + (int64_t)g0 * ix->dim, ix->dim, std::min<int32_t>(kTileLaunchMax, c - g0),
+                                            r.allow, tile + (int64_t)g0 * stride, stride)))
+                return rc;
+        for (int32_t i = tile_n > 0 ? c : 0; i < c; ++i)  // other dimensions: a score pass per query, same bits
+            if ((rc = launch_dense_scores_f64(ix, st, q + (int64_t)i * ix->dim, r.allow, tile + (int64_t)i * stride))) return rc;
+        (tile_n > 0 ? ix->rank_f64_tiled : ix->rank_f64_passed) += c;
+    } else {
+        const int64_t t0 = g.term_offsets[q0];
+        const int64_t nt = g.term_offsets[q0 + c] - t0;
+        if (nt > 0) ANRAG_HIP(hipMemcpyAsync(r.terms, g.term_ids + t0, (size_t)nt * 4, hipMemcpyHostToDevice, st));
+        r.h_segk.resize((size_t)c);  // (the run's own staging: it stays as it is until the chunk's host sync)
+        r.h_off.resize((size_t)c + 1);
+        for (int32_t q = 0; q < c; ++q) {
+            const int32_t n_terms = (int32_t)(g.term_offsets[q0 + q + 1] - g.term_offsets[q0 + q]);
+            r.h_segk[(size_t)q] = n_terms > 0 ? r.k : 0;  // no tokens: the leg is skipped (search_engine.py:216-217)
+        }
+        for (int32_t q = 0; q <= c; ++q) r.h_off[(size_t)q] = g.term_offsets[q0 + q] - t0;
+        ANRAG_HIP(hipMemcpyAsync(r.seg_k, r.h_segk.data(), (size_t)c * 4, hipMemcpyHostToDevice, st));
+        ANRAG_HIP(hipMemcpyAsync(r.term_off, r.h_off.data(), ((size_t)c + 1) * 8, hipMemcpyHostToDevice, st));
+        // K3 in its score-writing form, the chunk's queries in launches of up to 32,768 (a query without terms writes
+        // nothing: its segment is sorted to length 0)
+        double *tile = static_cast<double *>(r.scores);
+        for (int32_t g0 = 0; g0 < c; g0 += 32768)
+            if ((rc = launch_bm25_scores_table(ix, st, r.terms, r.term_off + g0, std::min<int32_t>(32768, c - g0), r.allow,
+                                               tile + (int64_t)g0 * stride, stride)))
+                return rc;
+    }
+    if (!count)
+        return launch_rank_sort(ix->device, st, c, r.scores, r.kind != ANRAG_LEG_DENSE, stride, (int32_t)r.rows, r.k, r.seg_k,
+                                r.list_rows, r.list_keys, r.k, r.list_cnt, r.wide);
+    // one list, rank of the expected document only: a count instead of the list
+    const RankTail &t = *count;
+    if (r.kind == ANRAG_LEG_DENSE)
+        rank_count_kernel<float><<<c, kRankThreads, 0, st>>>(static_cast<const float *>(r.scores), stride, (int32_t)r.rows, r.k,
+                                                            nullptr, t.leg[0].doc_of_row, t.out_n, t.d_expect, t.d_rank,
+                                                            t.d_out_cnt);
+    else
+        rank_count_kernel<double><<<c, kRankThreads, 0, st>>>(static_cast<const double *>(r.scores), stride, (int32_t)r.rows,
+                                                             r.k, r.seg_k, t.leg[0].doc_of_row, t.out_n, t.d_expect, t.d_rank,
+                                                             t.d_out_cnt);
+    ANRAG_HIP(hipGetLastError());
+    return ANRAG_OK;
+}
+
 }  // namespace anrag
 
 using namespace anrag;
@@ -1422,26 +1668,19 @@ extern "C" int anrag_rank_caps(int32_t *out_k_max_fp32, int32_t *out_k_max_fp64)
 extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int32_t n_queries, int32_t similarity_k,
                                 double wrrf_k, int32_t top_n, int64_t id_space, int64_t *out_id, double *out_score,
                                 int32_t *out_count, const int64_t *expect_id, int32_t *out_rank) {
-    ANRAG_REQUIRE(legs != nullptr && n_legs >= 1 && n_legs <= ANRAG_WRRF_MAX_LISTS, "n_legs %d out of range [1, %d]", n_legs,
-                  ANRAG_WRRF_MAX_LISTS);
-    ANRAG_REQUIRE(n_queries >= 0 && n_queries <= (1 << 22), "n_queries %d out of range", n_queries);
-    ANRAG_REQUIRE(similarity_k > 0 && top_n > 0, "similarity_k and top_n must be positive");
-    ANRAG_REQUIRE(out_count != nullptr, "out_count is NULL");
-    ANRAG_REQUIRE(!out_score || out_id, "out_score without out_id");
-    ANRAG_REQUIRE((expect_id != nullptr) == (out_rank != nullptr), "expect_id and out_rank come together");
-    ANRAG_REQUIRE(out_id || out_rank, "nothing to return: out_id and out_rank are both NULL");
+    RankPlan p;
+    int rc;
+    if ((rc = rank_plan_call(p, legs != nullptr, n_legs, n_queries, similarity_k, wrrf_k, top_n, id_space, out_id, out_score,
+                             out_count, expect_id, out_rank)))
+        return rc;
     if (n_queries == 0) return ANRAG_OK;
-    const bool fuse = n_legs > 1;
+    RankLegOps ops[ANRAG_WRRF_MAX_LISTS];
     int device = -1;
-    int64_t leg_rows[ANRAG_WRRF_MAX_LISTS];
-    int32_t leg_k[ANRAG_WRRF_MAX_LISTS];
-    int64_t sum_k = 0;
     for (int l = 0; l < n_legs; ++l) {
         const anrag_rank_leg &g = legs[l];
         ANRAG_REQUIRE(g.idx != nullptr, "leg %d: index handle is NULL", l);
-        ANRAG_REQUIRE(g.kind == ANRAG_LEG_DENSE || g.kind == ANRAG_LEG_BM25 || g.kind == ANRAG_LEG_DENSE_F64, "leg %d: kind %d", l,
-                      g.kind);
-        ANRAG_REQUIRE(g.weight > 0.0 && g.weight < __builtin_huge_val(), "leg %d: weight must be positive and finite", l);
+        ops[l] = rank_leg_ops(g);
+        if ((rc = rank_plan_kind(l, ops[l], 1u << ANRAG_LEG_DENSE | 1u << ANRAG_LEG_BM25 | 1u << ANRAG_LEG_DENSE_F64))) return rc;
         if (device < 0) device = g.idx->device;
         ANRAG_REQUIRE(g.idx->device == device, "leg %d lives on device %d, leg 0 on device %d", l, g.idx->device, device);
     }
@@ -1457,292 +1696,62 @@ extern "C" int anrag_rank_batch(const anrag_rank_leg *legs, int32_t n_legs, int3
         set_error("hipSetDevice(%d) failed", device);
         return ANRAG_ERR_HIP;
     }
-    for (int l = 0; l < n_legs; ++l) {
-        const anrag_rank_leg &g = legs[l];
-        if (g.kind == ANRAG_LEG_DENSE || g.kind == ANRAG_LEG_DENSE_F64) {
-            ANRAG_REQUIRE(g.idx->d_emb != nullptr, "leg %d: dense ranking before anrag_dense_load", l);
-            ANRAG_REQUIRE(g.queries != nullptr, "leg %d: queries is NULL", l);
-            ANRAG_REQUIRE(!(g.allow_source && !g.idx->d_dense_src), "leg %d: a source filter needs source ids", l);
-            leg_rows[l] = g.idx->n_rows;
-        } else {
-            ANRAG_REQUIRE(g.idx->d_post_doc != nullptr, "leg %d: BM25 ranking before anrag_bm25_load", l);
-            ANRAG_REQUIRE(g.term_offsets != nullptr && g.term_offsets[0] == 0, "leg %d: bad term offsets", l);
-            ANRAG_REQUIRE(g.term_offsets[n_queries] == 0 || g.term_ids != nullptr, "leg %d: term_ids is NULL", l);
-            for (int32_t q = 0; q < n_queries; ++q)
-                ANRAG_REQUIRE(g.term_offsets[q + 1] >= g.term_offsets[q] && g.term_offsets[q + 1] - g.term_offsets[q] <= 4096,
-                              "leg %d, query %d: term count out of range [0, 4096]", l, q);
-            ANRAG_REQUIRE(!(g.allow_source && !g.idx->d_bm25_src), "leg %d: a source filter needs source ids", l);
-            leg_rows[l] = g.idx->n_docs;
-        }
-        ANRAG_REQUIRE(leg_rows[l] < 0x7FFFFFFFll, "leg %d: %lld rows (the batched ranking takes < 2^31)", l,
-                      (long long)leg_rows[l]);
-        ANRAG_REQUIRE(!g.allow_source || (g.n_sources >= 0 && g.n_sources <= 65536), "leg %d: n_sources out of range", l);
-        leg_k[l] = (int32_t)std::min<int64_t>(similarity_k, leg_rows[l]);
-        const int32_t cap = g.kind == ANRAG_LEG_DENSE ? rank_cap<2>() : rank_cap<3>();
-        ANRAG_REQUIRE(leg_k[l] <= cap, "leg %d: min(similarity_k, rows) = %d is outside the batched ranking's envelope (%d)",
-                      l, leg_k[l], cap);
-        ANRAG_REQUIRE(leg_k[l] < (1 << kTiePosBits), "leg %d: list too long", l);
-        sum_k += leg_k[l];
-    }
-    bool fuse_in_lds = false;  // the id space fits one workgroup's LDS: rank_fuse_sort_kernel does the whole fusion
-    int32_t fuse_n = 0;  // entries the fused order is cut to
-    if (fuse) {
-        ANRAG_REQUIRE(id_space > 0 && id_space < 0x7FFFFFFFll, "id_space %lld out of range", (long long)id_space);
-        fuse_n = (int32_t)std::min<int64_t>(std::min<int64_t>(top_n, sum_k), id_space);
-        ANRAG_REQUIRE(fuse_n <= rank_cap<3>(), "min(top_n, entries) = %d is outside the batched ranking's envelope (%d)",
-                      fuse_n, rank_cap<3>());
-        fuse_in_lds = id_space <= rank_cap<3>() && !getenv("ANRAG_RANK_FUSE_IN_HBM");
-        const int64_t *maps[ANRAG_WRRF_MAX_LISTS];
-        for (int l = 0; l < n_legs; ++l) maps[l] = legs[l].doc_of_row;
-        if (int rc = rank_check_maps(n_legs, maps, leg_rows, id_space)) return rc;
-    }
-    for (anrag_index *o : owners)
-        if (int rc = settle_pipeline(o)) return rc;
-
     anrag_index *own = legs[0].idx;  // scratch and stream of the call
     hipStream_t st = own->primary;
+    RankLegRun run[ANRAG_WRRF_MAX_LISTS];
+    for (int l = 0; l < n_legs; ++l) {
+        anrag_index *ix = legs[l].idx;
+        if ((rc = rank_plan_index(l, ops[l], ix))) return rc;
+        if ((rc = rank_plan_leg(p, l, ops[l], ops[l].kind == ANRAG_LEG_BM25 ? ix->n_docs : ix->n_rows))) return rc;
+        run[l].ix = ix;
+        run[l].st = st;
+        run[l].kind = ops[l].kind;
+        run[l].rows = p.leg_rows[l];
+        run[l].stride = (p.leg_rows[l] + 63) / 64 * 64;
+        run[l].k = p.leg_k[l];
+    }
+    if ((rc = rank_plan_fusion(p, ops))) return rc;
+    for (anrag_index *o : owners)
+        if ((rc = settle_pipeline(o))) return rc;
+
     // ---- sizes: what one query of a chunk needs, and the per-call pieces
-    const int32_t out_n = fuse ? fuse_n : (int32_t)std::min<int64_t>(top_n, leg_k[0]);
-    int64_t per_query = 0, fixed = 0;
+    const bool fuse = p.fuse;
     for (int l = 0; l < n_legs; ++l) {
         const bool dense = legs[l].kind == ANRAG_LEG_DENSE, dense64 = legs[l].kind == ANRAG_LEG_DENSE_F64;
-        const int64_t stride = (leg_rows[l] + 63) / 64 * 64;
-        per_query += stride * (dense ? 4 : 8) + (int64_t)leg_k[l] * 4 + 256 + 4 + 4;
-        if (!fuse) per_query += (int64_t)leg_k[l] * 8 + 256;
+        const int64_t stride = (p.leg_rows[l] + 63) / 64 * 64;
+        p.per_query += stride * (dense ? 4 : 8) + (int64_t)p.leg_k[l] * 4 + 256 + 4 + 4;
+        if (!fuse) p.per_query += (int64_t)p.leg_k[l] * 8 + 256;
         // BM25: the query's offset into the chunk's terms
-        per_query += dense ? (int64_t)legs[l].idx->dim * 4 : (dense64 ? (int64_t)legs[l].idx->dim * 8 : 8);
-        fixed += 2048 * 4 + 256 + 8 + 256 + (legs[l].doc_of_row ? leg_rows[l] * 4 + 256 : 0);
+        p.per_query += dense ? (int64_t)legs[l].idx->dim * 4 : (dense64 ? (int64_t)legs[l].idx->dim * 8 : 8);
+        p.fixed += 2048 * 4 + 256 + 8 + 256 + (legs[l].doc_of_row ? p.leg_rows[l] * 4 + 256 : 0);
     }
-    if (fuse && !fuse_in_lds) per_query += id_space * 12 + 512 + (int64_t)fuse_n * 12 + 512 + 4;
-    if (fuse) per_query += 4 + 256;
-    fixed += 1024;
-    per_query += (int64_t)out_n * 16 + 4 + 512 + 16;
-    int64_t max_terms_chunk = 0;  // sized below, once the chunk is known
-    const int64_t budget = 6ll << 30;
-    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n_queries, (budget - fixed) / std::max<int64_t>(per_query, 1)));
-    if (chunk > 8) chunk = chunk / 8 * 8;
-    for (int l = 0; l < n_legs; ++l)
-        if (legs[l].kind == ANRAG_LEG_BM25)
-            for (int64_t q0 = 0; q0 < n_queries; q0 += chunk) {
-                const int64_t q1 = std::min<int64_t>(n_queries, q0 + chunk);
-                max_terms_chunk = std::max(max_terms_chunk, legs[l].term_offsets[q1] - legs[l].term_offsets[q0]);
-            }
-    // the wide select's scratch, one block that the launches of a chunk share (they follow each other on the stream): sized
-    // for a full chunk, so a shorter last chunk that asks for it finds it there only if the full ones did
-    const int32_t c_full = (int32_t)std::min<int64_t>(chunk, n_queries);
-    int64_t wide_bytes = 0;
-    for (int l = 0; l < n_legs; ++l) {
-        const bool f64 = legs[l].kind != ANRAG_LEG_DENSE;
-        if (rank_wide_wanted(f64, c_full, (int32_t)leg_rows[l])) wide_bytes = std::max(wide_bytes, rank_wide_bytes(f64, c_full));
-    }
-    if (fuse && !fuse_in_lds && rank_wide_wanted(true, c_full, (int32_t)id_space))
-        wide_bytes = std::max(wide_bytes, rank_wide_bytes(true, c_full));
-    const int64_t need = fixed + chunk * per_query + n_legs * (max_terms_chunk * 4 + 256) + (1 << 16) + wide_bytes;
-    int rc;
-    if ((rc = ensure_pool(own, own->rank_pool, need))) return rc;
-
-    Carver cv(own->rank_pool.p);
-    struct LegDev {
-        uint32_t *allow = nullptr;
-        int32_t *doc_of_row = nullptr;
-        float *q = nullptr;
-        double *q64 = nullptr;  // ANRAG_LEG_DENSE_F64
-        int32_t *terms = nullptr;
-        int32_t *seg_k = nullptr;
-        int64_t *term_off = nullptr;
-        void *scores = nullptr;
-        int64_t stride = 0;
-        uint32_t *rows = nullptr;
-        double *row_keys = nullptr;
-        int32_t *cnt = nullptr;
-    } ld[ANRAG_WRRF_MAX_LISTS];
-    std::vector<uint32_t> h_bits(2048);
-    std::vector<int32_t> h_map;
-    for (int l = 0; l < n_legs; ++l) {
-        const anrag_rank_leg &g = legs[l];
-        const bool dense = g.kind == ANRAG_LEG_DENSE;
-        ld[l].stride = (leg_rows[l] + 63) / 64 * 64;
-        if (g.allow_source) {
-            ld[l].allow = cv.take<uint32_t>(2048);
-            if (int rc = pack_allow_bits(g.allow_source, g.n_sources, h_bits.data())) return rc;
-            ANRAG_HIP(hipMemcpyAsync(ld[l].allow, h_bits.data(), 2048 * 4, hipMemcpyHostToDevice, st));
-            ANRAG_HIP(hipStreamSynchronize(st));  // h_bits is reused by the next leg
-        }
-        if (g.doc_of_row) {
-            ld[l].doc_of_row = cv.take<int32_t>(leg_rows[l]);
-            h_map.resize((size_t)leg_rows[l]);
-            for (int64_t r = 0; r < leg_rows[l]; ++r) h_map[(size_t)r] = (int32_t)g.doc_of_row[r];
-            ANRAG_HIP(hipMemcpyAsync(ld[l].doc_of_row, h_map.data(), (size_t)leg_rows[l] * 4, hipMemcpyHostToDevice, st));
-            ANRAG_HIP(hipStreamSynchronize(st));
-        }
-        if (dense) {
-            ld[l].q = cv.take<float>(chunk * g.idx->dim);
-            ld[l].scores = cv.take<float>(chunk * ld[l].stride);
-        } else if (g.kind == ANRAG_LEG_DENSE_F64) {
-            ld[l].q64 = cv.take<double>(chunk * g.idx->dim);
-            ld[l].scores = cv.take<double>(chunk * ld[l].stride);
-        } else {
-            ld[l].terms = cv.take<int32_t>(std::max<int64_t>(max_terms_chunk, 1));
-            ld[l].seg_k = cv.take<int32_t>(chunk);
-            ld[l].term_off = cv.take<int64_t>(chunk + 1);
-            ld[l].scores = cv.take<double>(chunk * ld[l].stride);
-        }
-        ld[l].rows = cv.take<uint32_t>(chunk * leg_k[l]);
-        ld[l].cnt = cv.take<int32_t>(chunk);
-        if (!fuse) ld[l].row_keys = cv.take<double>(chunk * leg_k[l]);
-    }
-    double *d_f = nullptr, *d_skey = nullptr;
-    uint32_t *d_t = nullptr, *d_stie = nullptr;
-    int32_t *d_scnt = nullptr;
-    if (fuse && !fuse_in_lds) {
-        d_f = cv.take<double>(chunk * id_space);
-        d_t = cv.take<uint32_t>(chunk * id_space);
-        d_stie = cv.take<uint32_t>(chunk * fuse_n);
-        d_skey = cv.take<double>(chunk * fuse_n);
-    }
-    if (fuse) d_scnt = cv.take<int32_t>(chunk);
-    uint64_t *d_fuse_legs = fuse_in_lds ? cv.take<uint64_t>(6 * ANRAG_WRRF_MAX_LISTS) : nullptr;
-    int64_t *d_out_id = cv.take<int64_t>(chunk * out_n);
-    double *d_out_score = cv.take<double>(chunk * out_n);
-    int32_t *d_out_cnt = fuse ? d_scnt : cv.take<int32_t>(chunk);
-    int64_t *d_expect = expect_id ? cv.take<int64_t>(chunk) : nullptr;
-    int32_t *d_rank = expect_id ? cv.take<int32_t>(chunk) : nullptr;
-    RankWide wide;
-    wide.scratch = wide_bytes ? cv.take<char>(wide_bytes) : nullptr;
-    wide.bytes = wide_bytes;
-    if (cv.at > own->rank_pool.bytes) {
-        set_error("internal: rank scratch carve %lld > pool %lld", (long long)cv.at, (long long)own->rank_pool.bytes);
-        return ANRAG_ERR_STATE;
-    }
+    rank_plan_chunk(p, ops);
 
     RankTail tail;  // everything behind the legs' lists: the same buffers for every chunk
     tail.device = device;
     tail.st = st;
-    tail.n_legs = n_legs;
-    for (int l = 0; l < n_legs; ++l)
-        tail.leg[l] = RankTailLeg{ld[l].rows, ld[l].row_keys, ld[l].cnt, ld[l].doc_of_row, leg_k[l], legs[l].weight};
-    tail.fuse_in_lds = fuse_in_lds;
-    tail.wrrf_k = wrrf_k;
-    tail.id_space = id_space;
-    tail.fuse_n = fuse_n;
-    tail.out_n = out_n;
-    tail.d_f = d_f;
-    tail.d_t = d_t;
-    tail.d_stie = d_stie;
-    tail.d_skey = d_skey;
-    tail.d_scnt = d_scnt;
-    tail.d_fuse_legs = d_fuse_legs;
-    tail.d_out_id = d_out_id;
-    tail.d_out_score = d_out_score;
-    tail.d_out_cnt = d_out_cnt;
-    tail.d_expect = d_expect;
-    tail.d_rank = d_rank;
-    tail.wide = wide;
-    if (fuse_in_lds) {  // the legs' lists, counts, maps, strides and weights: the same for every chunk
-        uint64_t tab[6 * ANRAG_WRRF_MAX_LISTS];
-        rank_fuse_table(tail, tab);
-        ANRAG_HIP(hipMemcpyAsync(d_fuse_legs, tab, sizeof(tab), hipMemcpyHostToDevice, st));
-        ANRAG_HIP(hipStreamSynchronize(st));
-    }
-    const bool count_only = !fuse && out_id == nullptr;  // (then out_rank is wanted: checked above)
-    std::vector<int32_t> h_segk;
-    std::vector<int64_t> h_off;
-    for (int64_t q0 = 0; q0 < n_queries; q0 += chunk) {
-        const int32_t c = (int32_t)std::min<int64_t>(chunk, n_queries - q0);
-        if (expect_id) {
-            ANRAG_HIP(hipMemcpyAsync(d_expect, expect_id + q0, (size_t)c * 8, hipMemcpyHostToDevice, st));
-            ANRAG_HIP(hipMemsetAsync(d_rank, 0xFF, (size_t)c * 4, st));  // -1: not in the answer
-        }
-        for (int l = 0; l < n_legs; ++l) {
-            const anrag_rank_leg &g = legs[l];
-            anrag_index *ix = g.idx;
-            if (g.kind == ANRAG_LEG_DENSE) {
-                ANRAG_HIP(hipMemcpyAsync(ld[l].q, g.queries + q0 * ix->dim, (size_t)c * ix->dim * sizeof(float),
-                                         hipMemcpyHostToDevice, st));
-                float *tile = static_cast<float *>(ld[l].scores);
-                const int tile_n = getenv("ANRAG_RANK_SCAN_TILES") ? 0 : dense_tile_group_max(ix);
-                for (int32_t g0 = 0; tile_n > 0 && g0 < c; g0 += kTileLaunchMax)  // K1T: the rows once per launch
-                    if ((rc = launch_dense_tile(ix, st, ld[l].q + (int64_t)g0 * ix->dim, ix->dim,
-                                                std::min<int32_t>(kTileLaunchMax, c - g0), ld[l].allow,
-                                                tile + (int64_t)g0 * ld[l].stride, ld[l].stride)))
-                        return rc;
-                for (int32_t g0 = tile_n > 0 ? c : 0; g0 < c; g0 += kScanGroupMax) {  // other dimensions: a pass per query
-                    const int n = std::min<int32_t>(kScanGroupMax, c - g0);
-                    const float *qs[kScanGroupMax];
-                    int sets[kScanGroupMax];
-                    for (int i = 0; i < n; ++i) {
-                        qs[i] = ld[l].q + (int64_t)(g0 + i) * ix->dim;
-                        sets[i] = 0;  // unused: scores are written, no lists
-                    }
-                    if ((rc = launch_dense_scan_group(ix, st, qs, n, 0, ld[l].allow, tile + (int64_t)g0 * ld[l].stride, sets,
-                                                      ld[l].stride)))
-                        return rc;
-                }
-                if (count_only)  // one list, rank of the expected document only: a count instead of the list
-                    rank_count_kernel<float><<<c, kRankThreads, 0, st>>>(tile, ld[l].stride, (int32_t)leg_rows[l], leg_k[l], nullptr,
-                                                                        ld[l].doc_of_row, out_n, d_expect, d_rank, d_out_cnt);
-                else if ((rc = launch_seg_sort<float, false>(device, st, c, tile, ld[l].stride, nullptr, 0, (int32_t)leg_rows[l],
-                                                             leg_k[l], nullptr, ld[l].rows, ld[l].row_keys, leg_k[l], ld[l].cnt,
-                                                             wide)))
-                    return rc;
-            } else if (g.kind == ANRAG_LEG_DENSE_F64) {
-                // float64 queries: fp64 score tiles (K1TD, dense_tile_f64.hip), then the BM25 leg's path for an fp64 tile
-                ANRAG_HIP(hipMemcpyAsync(ld[l].q64, reinterpret_cast<const double *>(g.queries) + q0 * ix->dim,
-                                         (size_t)c * ix->dim * sizeof(double), hipMemcpyHostToDevice, st));
-                double *tile = static_cast<double *>(ld[l].scores);
-                const int tile_n = getenv("ANRAG_RANK_SCAN_TILES") ? 0 : dense_tile_f64_group_max(ix);
-                for (int32_t g0 = 0; tile_n > 0 && g0 < c; g0 += kTileLaunchMax)  // the rows once per group of queries
-                    if ((rc = launch_dense_tile_f64(ix, st, ld[l].q64 + (int64_t)g0 * ix->dim, ix->dim,
-                                                    std::min<int32_t>(kTileLaunchMax, c - g0), ld[l].allow,
-                                                    tile + (int64_t)g0 * ld[l].stride, ld[l].stride)))
-                        return rc;
-                for (int32_t q = tile_n > 0 ? c : 0; q < c; ++q)  // other dimensions: a score pass per query, same bits
-                    if ((rc = launch_dense_scores_f64(ix, st, ld[l].q64 + (int64_t)q * ix->dim, ld[l].allow,
-                                                      tile + (int64_t)q * ld[l].stride)))
-                        return rc;
-                (tile_n > 0 ? ix->rank_f64_tiled : ix->rank_f64_passed) += c;
-                if (count_only)
-                    rank_count_kernel<double><<<c, kRankThreads, 0, st>>>(tile, ld[l].stride, (int32_t)leg_rows[l], leg_k[l],
-                                                                         nullptr, ld[l].doc_of_row, out_n, d_expect, d_rank,
-                                                                         d_out_cnt);
-                else if ((rc = launch_seg_sort<double, false>(device, st, c, tile, ld[l].stride, nullptr, 0,
-                                                              (int32_t)leg_rows[l], leg_k[l], nullptr, ld[l].rows,
-                                                              ld[l].row_keys, leg_k[l], ld[l].cnt, wide)))
-                    return rc;
-            } else {
-                const int64_t t0 = g.term_offsets[q0];
-                const int64_t nt = g.term_offsets[q0 + c] - t0;
-                if (nt > 0)
-                    ANRAG_HIP(hipMemcpyAsync(ld[l].terms, g.term_ids + t0, (size_t)nt * 4, hipMemcpyHostToDevice, st));
-                h_segk.resize(c);
-                double *tile = static_cast<double *>(ld[l].scores);
-                for (int32_t q = 0; q < c; ++q) {
-                    const int32_t n_terms = (int32_t)(g.term_offsets[q0 + q + 1] - g.term_offsets[q0 + q]);
-                    h_segk[q] = n_terms > 0 ? leg_k[l] : 0;  // no tokens: the leg is skipped (search_engine.py:216-217)
-                }
-                ANRAG_HIP(hipMemcpyAsync(ld[l].seg_k, h_segk.data(), (size_t)c * 4, hipMemcpyHostToDevice, st));
-                h_off.resize((size_t)c + 1);
-                for (int32_t q = 0; q <= c; ++q) h_off[q] = g.term_offsets[q0 + q] - t0;
-                ANRAG_HIP(hipMemcpyAsync(ld[l].term_off, h_off.data(), ((size_t)c + 1) * 8, hipMemcpyHostToDevice, st));
-                ANRAG_HIP(hipStreamSynchronize(st));  // h_segk and h_off are reused
-                // K3 in its score-writing form, the chunk's queries in launches of up to 32,768 (a query without terms
-                // writes nothing: its segment is sorted to length 0)
-                for (int32_t g0 = 0; g0 < c; g0 += 32768)
-                    if ((rc = launch_bm25_scores_table(ix, st, ld[l].terms, ld[l].term_off + g0, std::min<int32_t>(32768, c - g0),
-                                                       ld[l].allow, tile + (int64_t)g0 * ld[l].stride, ld[l].stride)))
-                        return rc;
-                if (count_only)
-                    rank_count_kernel<double><<<c, kRankThreads, 0, st>>>(tile, ld[l].stride, (int32_t)leg_rows[l], leg_k[l],
-                                                                         ld[l].seg_k, ld[l].doc_of_row, out_n, d_expect, d_rank,
-                                                                         d_out_cnt);
-                else if ((rc = launch_seg_sort<double, false>(device, st, c, tile, ld[l].stride, nullptr, 0,
-                                                              (int32_t)leg_rows[l], leg_k[l], ld[l].seg_k, ld[l].rows,
-                                                              ld[l].row_keys, leg_k[l], ld[l].cnt, wide)))
-                    return rc;
+    int32_t *d_map[ANRAG_WRRF_MAX_LISTS] = {};
+    if ((rc = carve_pool(own, own->rank_pool, 256, [&](Carver &cv) {
+            for (int l = 0; l < n_legs; ++l) {
+                run[l].carve(cv, p, ops[l].allow_source != nullptr, !fuse);
+                d_map[l] = ops[l].doc_of_row ? cv.take<int32_t>(p.leg_rows[l]) : nullptr;
             }
-        }
+            tail.carve(cv, p, expect_id != nullptr);
+        })))
+        return rc;
+    for (int l = 0; l < n_legs; ++l) {
+        if ((rc = rank_stage_allow(run[l], ops[l]))) return rc;
+        if (d_map[l] && (rc = rank_stage_map(st, ops[l].doc_of_row, p.leg_rows[l], d_map[l]))) return rc;
+        tail.leg[l] = RankTailLeg{run[l].list_rows, run[l].list_keys, run[l].list_cnt, d_map[l], p.leg_k[l], ops[l].weight};
+    }
+    if ((rc = rank_stage_fuse_table(tail))) return rc;
+    const bool count_only = !fuse && out_id == nullptr;  // (then out_rank is wanted: checked above)
+    for (int64_t q0 = 0; q0 < n_queries; q0 += p.chunk) {
+        const int32_t c = (int32_t)std::min<int64_t>(p.chunk, n_queries - q0);
+        if ((rc = rank_stage_expect(tail, expect_id, q0, c))) return rc;
+        for (int l = 0; l < n_legs; ++l)
+            if ((rc = rank_leg_chunk(run[l], ops[l], q0, c, count_only ? &tail : nullptr))) return rc;
         if (!count_only && (rc = launch_rank_tail(tail, c, out_id != nullptr))) return rc;
-        ANRAG_HIP(hipGetLastError());
         if ((rc = rank_copy_out(tail, c, q0, top_n, out_id, out_score, out_count, out_rank))) return rc;
     }
     return ANRAG_OK;

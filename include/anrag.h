@@ -742,7 +742,8 @@ int anrag_shard_group_debug_enqueue(anrag_shard_group *g, int64_t *out_groups, i
  * staged with hipMemcpyPeerAsync.  One host sync per chunk; the steady state allocates nothing.
  * One leg with out_id == NULL: anrag_rank_batch counts instead of sorting; here the lists are formed all the same and
  * the rank is read from them (same ranks and counts).
- * ANRAG_RANK_CHUNK_BUDGET (bytes, measurements and tests only) replaces the 6 GiB of scratch a chunk may take. */
+ * ANRAG_RANK_CHUNK_BUDGET (bytes, measurements and tests only) replaces the 6 GiB of scratch a chunk may take, here and
+ * in anrag_rank_batch. */
 typedef struct anrag_group_rank_leg {
     anrag_shard_group *group;
     anrag_index *idx;

@@ -184,6 +184,75 @@ def test_expected_rank_equals_position_in_the_list(c1):
             assert ranks[i] == (pos[0] + 1 if len(pos) else -1), (i, k, top_n)
 
 
+def test_single_route_in_chunks_equals_one_chunk(monkeypatch):
+    """`ANRAG_RANK_CHUNK_BUDGET` cuts the single index's call into chunks of queries: 21 queries as 16 + 5 or 8 + 8 + 5,
+    and as a chunk per query, return the ids, counts, ranks and score bits of the one chunk the default budget makes of
+    them (that answer is pinned by the oracle tests above).  Queries without term ids sit at the end of the list and at
+    the end of the first chunk of 8; the offsets into the term ids, `expect` and the out arrays, and the short last
+    chunk, are what can go wrong."""
+    from anrag.bm25_index import Bm25Index
+    from anrag.index import Index, rank_batch
+
+    rng = np.random.default_rng(611)
+    n, d, nq, vocab = 600, 64, 21, 300
+    e = rng.standard_normal((n, d), dtype=np.float32)
+    e[301] = e[12]
+    q = rng.standard_normal((nq, d), dtype=np.float32)
+    docs = [[f"t{int(j)}" for j in rng.integers(0, vocab, size=int(rng.integers(3, 30)))] for _ in range(n)]
+    bi = Bm25Index(docs, k1=1.7, b=0.83, epsilon=0.05)
+    tl = [bi.term_ids([str(t) for t in rng.choice(docs[int(rng.integers(n))], size=int(rng.integers(2, 8)))])
+          for _ in range(nq)]
+    for i in (2, 7, 20):
+        tl[i] = np.zeros(0, np.int32)
+    has_terms = np.array([len(t) > 0 for t in tl])
+    perm = rng.permutation(n).astype(np.int64)
+    expect = rng.integers(0, n, nq).astype(np.int64)
+    with Index(0) as ix:
+        ix.dense_load(e)
+        ix.bm25_load(bi.indptr, bi.post_doc, bi.post_tf, bi.idf, bi.doc_len, bi.avgdl, bi.k1, bi.b)
+        dense = dict(index=ix, weight=5.0, queries=q)
+        bm25 = dict(index=ix, weight=1.0, term_lists=tl)
+        fused = dict(id_space=n, want_scores=True)
+        # (legs, k, keywords, fusion in HBM, the queries that must have an answer)
+        shapes = [([dense, bm25], n, fused, False, np.ones(nq, bool)),
+                  ([dense, bm25], n, fused, True, np.ones(nq, bool)),
+                  ([dense], n, dict(expect=expect, want_ids=False), False, np.ones(nq, bool)),
+                  ([bm25], n, dict(expect=expect, want_ids=False), False, has_terms),
+                  ([dict(index=ix, weight=1.0, queries_f64=q.astype(np.float64))], 25, dict(want_scores=True), False,
+                   np.ones(nq, bool)),
+                  ([dict(index=ix, weight=1.0, queries=q, doc_of_row=perm)], n, dict(want_scores=True), False,
+                   np.ones(nq, bool))]
+        for legs, k, kw, in_hbm, answered in shapes:
+            # bytes of scratch a query of a chunk takes, from the sizes: every leg's scores and query, its list (rows,
+            # keys), the fused sums and their sorted cut where the fusion runs in HBM, the output records
+            per_query = sum(n * (4 if "queries" in l else 8) + k * 12 + d * 8 for l in legs) + k * 16
+            if in_hbm:
+                per_query += n * 12 + k * 12
+            per_call = 32768 + sum(n * 4 for l in legs if l.get("doc_of_row") is not None)
+            assert 2 * (nq * per_query + per_call) < 6 << 30  # the default budget: one chunk
+
+            def call():
+                if in_hbm:
+                    monkeypatch.setenv("ANRAG_RANK_FUSE_IN_HBM", "1")
+                try:
+                    return rank_batch(legs, nq, k, 40.0, k, **kw)
+                finally:
+                    monkeypatch.delenv("ANRAG_RANK_FUSE_IN_HBM", raising=False)
+
+            monkeypatch.delenv("ANRAG_RANK_CHUNK_BUDGET", raising=False)
+            want = call()
+            assert want[2][answered].min() >= 1  # two empty answers cannot agree
+            for budget in (12 * per_query + per_call, 1):  # a first chunk of 8 or 16 queries; a chunk per query
+                monkeypatch.setenv("ANRAG_RANK_CHUNK_BUDGET", str(budget))
+                got = call()
+                monkeypatch.delenv("ANRAG_RANK_CHUNK_BUDGET")
+                for w, g in zip(want, got):
+                    assert (w is None) == (g is None), (len(legs), k, budget)
+                    if w is not None:
+                        w, g = (a.view(np.int64) if a.dtype == np.float64 else a for a in (w, g))
+                        assert np.array_equal(w, g), (len(legs), k, in_hbm, budget)
+
+
 @pytest.mark.parametrize("d", [64, 128, 192, 256, 320, 384, 448, 512, 640, 768, 896, 1024, 1536, 2048, 3072, 8])
 def test_score_tiles_equal_the_scan_scores_at_every_kernel_shape(d):
     """K1T (dense_tile.hip: a batch of rows in registers, all the queries of a launch over it) against K1's own score
